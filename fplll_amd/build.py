@@ -119,7 +119,8 @@ def build_gso_dropin(force=False):
     """libfplll_hip_gso.so: MatGSOHip + the LLLReduction::lll / babai specialisations and MatHouseholderHip + the
     HLLLReduction::hlll specialisation (csrc/dropin/), host C++
     against fplll's own headers — what a maintainer builds inside fplll's tree.  Where the headers
-    are absent (the GPU box) the prebuilt library that travelled with the tree is used."""
+    are absent there is nothing to build; the reference drivers under oracle/_ref/ link a copy of their
+    own (oracle/Makefile)."""
     out = os.path.join(LIBDIR, "libfplll_hip_gso.so")
     src = os.path.join(CSRC, "dropin", "matgso_hip.cpp")
     src2 = os.path.join(CSRC, "dropin", "mathouseholder_hip.cpp")
