@@ -43,6 +43,11 @@ __global__ void enum_walk_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf o
                                  unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
                                  unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
                                  const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
+template <bool MU_LDS, bool DUAL>
+__global__ void enum_chain_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, unsigned task_lo,
+                                  unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
+                                  unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
+                                  const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
 // enum_deal.hip: the content-sorted snake deal of a multi-rank call on the device
 size_t deal_work_bytes(unsigned n);
 unsigned deal_tasks_device(hipStream_t s, const unsigned long long *keys, const double *pd, const unsigned *slot_of,
@@ -910,6 +915,7 @@ restart:
 
   const int debug     = env_int("FPHIP_DEBUG", 0);
   const bool walk2    = env_int("FPHIP_WALK2", 1) != 0;
+  const bool walk3    = env_int("FPHIP_WALK3", 1) != 0;
   uint64_t nsol       = 0;
   double kernel_ms    = top_ms, final_ms = 0.0;
   int launches        = 0;
@@ -1226,14 +1232,23 @@ restart:
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],          \
                      (regioned && !shard_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
                      (unsigned long long)__atomic_load_n(&ctx->h->bound_bits, __ATOMIC_ACQUIRE))
-        // the walk launches (no sub-solutions): the second-generation walk — all children of a node in one vector
-        // test (enum_walk.hip); FPHIP_WALK2=0 keeps enum_phase_kernel (the A/B partner)
-#define FPHIP_LAUNCH2(M, D)                                                                          \
-  hipLaunchKernelGGL((enum_walk_kernel<M, D>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g,  \
+        // the walk launches (no sub-solutions): the third-generation walk — single-child descents store nothing,
+        // the next sibling is one scalar search (enum_walk3.hip); FPHIP_WALK3=0 keeps the second generation
+        // (enum_walk.hip), FPHIP_WALK2=0 enum_phase_kernel (the A/B partners)
+#define FPHIP_LAUNCH2_K(KERNEL)                                                                      \
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g,                   \
                      ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,           \
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],  \
                      (regioned && !shard_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
                      (unsigned long long)__atomic_load_n(&ctx->h->bound_bits, __ATOMIC_ACQUIRE))
+#define FPHIP_LAUNCH2(M, D)                                                                          \
+  do                                                                                                 \
+  {                                                                                                  \
+    if (walk3)                                                                                       \
+      FPHIP_LAUNCH2_K((enum_chain_kernel<M, D>));                                                    \
+    else                                                                                             \
+      FPHIP_LAUNCH2_K((enum_walk_kernel<M, D>));                                                     \
+  } while (0)
         if (in_final && !subs && walk2)
         {
           if (dual && mu_lds)
@@ -1259,6 +1274,7 @@ restart:
           FPHIP_LAUNCH(false, true, false);
 #undef FPHIP_LAUNCH
 #undef FPHIP_LAUNCH2
+#undef FPHIP_LAUNCH2_K
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         ++launch_idx;
@@ -1363,6 +1379,8 @@ restart:
   HIPCHK(ctx, hipMemcpy(st, ctx->g, offsetof(DevShared, task_head), hipMemcpyDeviceToHost));
   if (st->error_flags & FPHIP_ERR_RING_TIMEOUT)
     return fail(ctx, "device timed out waiting for the host ring consumer");
+  if (debug)
+    fprintf(stderr, "[fphip s%d] path replays of the chain walk: %u\n", o.shard_index, st->replays);
   uint64_t total = 0;
   for (int k = 0; k <= d; ++k)
     nodes_out[k] = (k < d) ? st->nodes[k] : 0;
