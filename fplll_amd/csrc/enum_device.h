@@ -61,7 +61,7 @@ struct DevShared
   unsigned long long iters;     // walk-loop iterations (diagnostics)
   unsigned long long bound_bits;  // device mirror of HostCtl::bound_bits (only ever lowered)
   unsigned int error_flags;
-  unsigned int replays;  // path replays of enum_chain_kernel (enum_walk3.hip) in this call (diagnostics)
+  unsigned int replays;  // path replays of the third-generation walk (enum_walk.hip, CHAIN) in this call (diagnostics)
   unsigned int task_head[FPHIP_MAX_LAUNCHES];
   unsigned int drain[FPHIP_MAX_LAUNCHES];  // set when a launch's task queue ran dry
   double rp[256][2];  // (rdiag[k], pruning[k]) interleaved: one 16-byte scalar load per level

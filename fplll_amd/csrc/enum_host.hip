@@ -38,16 +38,11 @@ __global__ void enum_top_kernel(DevShared *g, HostCtl *h, TopBuf in, unsigned n_
                                 int count_nodes, int launch_idx, double *gtop);
 __global__ void task_key_kernel(TaskBuf in, unsigned n, int d, unsigned long long *keys,
                                 const double *xhi_root, const unsigned *slots);
-template <bool MU_LDS, bool DUAL>
+template <bool MU_LDS, bool DUAL, bool CHAIN>
 __global__ void enum_walk_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, unsigned task_lo,
                                  unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
                                  unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
                                  const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
-template <bool MU_LDS, bool DUAL>
-__global__ void enum_chain_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, unsigned task_lo,
-                                  unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
-                                  unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
-                                  const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
 // enum_deal.hip: the content-sorted snake deal of a multi-rank call on the device
 size_t deal_work_bytes(unsigned n);
 unsigned deal_tasks_device(hipStream_t s, const unsigned long long *keys, const double *pd, const unsigned *slot_of,
@@ -1233,10 +1228,10 @@ restart:
                      (regioned && !shard_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
                      (unsigned long long)__atomic_load_n(&ctx->h->bound_bits, __ATOMIC_ACQUIRE))
         // the walk launches (no sub-solutions): the third-generation walk — single-child descents store nothing,
-        // the next sibling is one scalar search (enum_walk3.hip); FPHIP_WALK3=0 keeps the second generation
-        // (enum_walk.hip), FPHIP_WALK2=0 enum_phase_kernel (the A/B partners)
-#define FPHIP_LAUNCH2_K(KERNEL)                                                                      \
-  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g,                   \
+        // the next sibling is one scalar search (enum_walk_kernel<.., CHAIN = true>, enum_walk.hip); FPHIP_WALK3=0
+        // keeps the second generation (<.., false>), FPHIP_WALK2=0 enum_phase_kernel (the A/B partners)
+#define FPHIP_LAUNCH2_K(M, D, C)                                                                     \
+  hipLaunchKernelGGL((enum_walk_kernel<M, D, C>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
                      ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,           \
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],  \
                      (regioned && !shard_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
@@ -1245,9 +1240,9 @@ restart:
   do                                                                                                 \
   {                                                                                                  \
     if (walk3)                                                                                       \
-      FPHIP_LAUNCH2_K((enum_chain_kernel<M, D>));                                                    \
+      FPHIP_LAUNCH2_K(M, D, true);                                                                   \
     else                                                                                             \
-      FPHIP_LAUNCH2_K((enum_walk_kernel<M, D>));                                                     \
+      FPHIP_LAUNCH2_K(M, D, false);                                                                  \
   } while (0)
         if (in_final && !subs && walk2)
         {

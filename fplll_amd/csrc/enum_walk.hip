@@ -1,19 +1,22 @@
-// enum_walk.hip — the walk launches of the enumeration, second generation: ALL children of a node in one
-// vector test.
+// enum_walk.hip — the walk launches of the enumeration: ALL children of a node in one vector test (the second
+// generation, enum_walk_kernel<.., CHAIN = false>), and around the same test the bookkeeping that makes the chain
+// the common case (the third generation, <.., CHAIN = true>).  ONE kernel text: what the generations share appears
+// once, every place where they differ is an `if constexpr (CHAIN)`.
 //
 // Reference behaviour reproduced (fplll v5.5.0): EnumerationBase::enumerate_recursive,
 // fplll/enum/enumerate_base.cpp:24-118 (centre, roundto, zig-zag order :80-92, bound test :31 / :93, node
 // counting :33, the dual recursion :57-61 / :103-105) with the bounds of EnumerationDyn
 // (enumerate.cpp:218-239).  Same visit set, same arithmetic per node (separate multiply / add, the reference's
 // operand order), same per-level counts and candidates as enum_phase_kernel (enum_kernel.hip) — which stays the
-// kernel of the split launches, of sub-solution calls and the A/B partner of this one (FPHIP_WALK2=0).
+// kernel of the split launches, of sub-solution calls and the A/B partner of these (FPHIP_WALK2=0).  The final walk
+// launches run the third generation; FPHIP_WALK3=0 selects the second, its A/B partner.
 //
-// What changed, and why.  enum_phase_kernel visits the children of a node one test at a time: the first child in
-// its CHILD chain, every later sibling in its STEP loop, and every node's sibling sequence ENDS with a failing
-// test — per counted node one successful and one failing test, 40.5 vector + 38.8 scalar / branch instructions,
-// 0.81 of the vector issue port (profiles/r05_enum_pmc_summary.txt).  The siblings of a node, however, are a
-// function of three wave-uniform numbers (the centre c, the parent's distance, r_kk): child j of the zig-zag has
-// x_j = round(c) + z_j, dist_j = pd + (x_j - c)^2 r, and the sequence of distances is non-decreasing.  This
+// The second generation: what changed, and why.  enum_phase_kernel visits the children of a node one test at a
+// time: the first child in its CHILD chain, every later sibling in its STEP loop, and every node's sibling sequence
+// ENDS with a failing test — per counted node one successful and one failing test, 40.5 vector + 38.8 scalar /
+// branch instructions, 0.81 of the vector issue port (profiles/r05_enum_pmc_summary.txt).  The siblings of a node,
+// however, are a function of three wave-uniform numbers (the centre c, the parent's distance, r_kk): child j of the
+// zig-zag has x_j = round(c) + z_j, dist_j = pd + (x_j - c)^2 r, and the sequence of distances is non-decreasing.  This
 // kernel evaluates the 64 first candidates of a node in the 64 LANES — one fma, one subtract, two multiplies, one
 // add, one compare — and reads the number of surviving children off the ballot (s_ff1 of its complement): the
 // failing test is gone and the later siblings need no test at all (STEP: the next index of the stored count).
@@ -37,6 +40,24 @@
 // shortens their counts (reprune): a sibling is never visited under a bound it fails, to the granularity at which
 // waves learn of a new bound — enum_phase_kernel's contract as well.
 //
+// The third generation (CHAIN): the chain is the common case.  Same visit set, arithmetic, counting rule and
+// candidates as the second, whose EXPAND test (all children of a node in one 64-lane test) it keeps.  What changed is
+// the bookkeeping around it.  Two thirds of the nodes of the flagship tree have exactly one surviving child
+// (DESIGN.md section 3), and the second generation paid for sibling state on every one of them: the column push, six
+// selects and a writelane for (c, x_0, pd, st) — none of it ever read back when n = 1 — and, on the way up, one
+// readlane-compare-branch iteration per level.
+//
+// Sibling state lives in two wave-uniform 64-bit masks (SGPRs), bit l = level l:
+//   P  level l has a sibling left (a hot level with i + 1 < n, or a slow level that is not exhausted).  Invariant:
+//      no bit below the level of the current node is set.  STEP is therefore ONE scalar search: the lowest set bit
+//      of P is the level of the next sibling; an empty P ends the task.
+//   B  level l's lane registers (cs, x0s, pds, st) and its pushed column are valid: set by an expansion with n >= 2
+//      and by the slow levels (zero chain, 63+ children), cleared by a chain descent.  P implies B.
+// A chain descent (n = 1) counts the child, takes its distance and column and clears B: no push, no lane-register
+// write.  The coefficient of a level outside B is roundto(centre) and is not stored: the three rare paths that need
+// the coefficients of the path (a level-1 leaf report, the prefix of a donated task) replay the path from the task's
+// root column with the walk's own operation sequence, so the bits are identical; reprune touches B levels only.
+//
 // Build: like enum_kernel.hip (-ffp-contract=off; -structurizecfg-skip-uniform-regions, no lifetime markers).
 
 #include <hip/hip_runtime.h>
@@ -48,14 +69,15 @@
 namespace fphip
 {
 
-// st: the sibling state of one level (lane = level)
+// st: the sibling state of one level (lane = level; CHAIN: of one B level)
 //   hot level     bits 0-6: i, the index of the current child in zig-zag order (0..61); bits 8-14: n, the number of
-//                 surviving children (1..62); the direction of the first step is not stored: it is c >= x_0 again
+//                 surviving children (1..62; CHAIN: 2..62); the direction of the first step is not stored: it is
+//                 c >= x_0 again
 //   slow level    (st & 0x7fff) == ST_MARK (i = 100 < n = 127: "a sibling is left" for the hot test, which sends
 //                 every i >= 64 to the general path); bits 17-31: iw, the index of the current child.  Levels of the
-//                 zero chain, levels with 63+ surviving children — and lane Lt & 63, the task root's: the climb
-//                 that reaches it ends the task
-//   0             nothing left at this level
+//                 zero chain, levels with 63+ surviving children — and, without CHAIN, lane Lt & 63, the task root's:
+//                 the climb that reaches it ends the task
+//   0             (without CHAIN) nothing left at this level
 #define ST_I(s) ((s)&0x7f)
 #define ST_N(s) (((s) >> 8) & 0x7f)
 #define ST_MARK 0x7f64
@@ -80,7 +102,7 @@ __device__ __forceinline__ v2u r_issue(const double *tab, unsigned off)
 __device__ __forceinline__ void rp_wait(v2u &q) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(q)); }
 __device__ __forceinline__ double rp_r2(const v2u &q) { return __hiloint2double((int)q.y, (int)q.x); }
 
-template <bool MU_LDS, bool DUAL>
+template <bool MU_LDS, bool DUAL, bool CHAIN>
 __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
     enum_walk_kernel(DevShared *__restrict__ g, HostCtl *__restrict__ h, TaskBuf in, TaskBuf out,
                      int d, int Lmax, unsigned task_lo, unsigned task_hi,
@@ -226,9 +248,15 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
              : (idxlist ? (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)idxlist[pos]) : pos);
     const int Lt      = __builtin_amdgcn_readfirstlane(in.level[ti]);
     const int rid     = __builtin_amdgcn_readfirstlane(in.root[ti]);
-    const int tl      = here_lane(lane);
-    const double xpre = in.x[ti * 64 + tl];
-    const double col0 = in.col[ti * 64 + tl];
+    // (without CHAIN the task's coefficients and column are read up front; with it the column only, below: in.x is
+    //  read inside path_x)
+    double xpre = 0.0, col0 = 0.0;
+    if constexpr (!CHAIN)
+    {
+      const int tl = here_lane(lane);
+      xpre         = in.x[ti * 64 + tl];
+      col0         = in.col[ti * 64 + tl];
+    }
     const double pd0  = in.pd[ti];
     int donate        = 1 << 20;
     const unsigned iter0 = iter;
@@ -239,22 +267,68 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
 
     int k     = Lt;
     double S  = col0;
+    if constexpr (CHAIN)
+      S = in.col[ti * 64 + here_lane(lane)];
     double nd = pd0;
     // the chain of first children below a root of distance exactly 0 goes through the general path (slow
     // levels) until the first step away from it: every level is "special" while zc holds
     bool zc = __builtin_amdgcn_ballot_w64(pd0 != 0.0) == 0ull;
-    // the climb that reaches the root's level ends the task: a slow marker in its lane (lane 0 when Lt = 64 —
+    // CHAIN: the sibling masks (see the header): the task root's level holds no sibling, an empty P ends the task
+    unsigned long long P = 0ull, B = 0ull;
+    // else: the climb that reaches the root's level ends the task: a slow marker in its lane (lane 0 when Lt = 64 —
     // level 0 keeps no sibling state: its nodes are the leaf loop's)
-    st = (lane == (Lt & 63)) ? ST_MARK : st;
+    if constexpr (!CHAIN)
+      st = (lane == (Lt & 63)) ? ST_MARK : st;
 
-    // the coefficients of the current path (lane = level): x_0 + z(i) of each level's sibling state
+    // The coefficients of the current path (lane = level), levels >= Lt from the task.  Without CHAIN every level
+    // keeps its sibling state: x_0 + z(i) of it.  (A lambda of its own ahead of the others, as the second generation
+    // always had it: folded into path_x it changes the order in which the compiler promotes the captured level
+    // registers, and with that the register copies of the second generation's kernels — tests/perf/walk_isa_diff.py.)
     auto xs_now = [&]() -> double
     {
       const int idx = (lane == 0) ? 0 : (ST_IS_SLOW(st) ? ST_IW(st) : ST_I(st));
       return x0s + (double)zig_of(idx, !(cs >= x0s));
     };
+    auto path_x = [&](int klo) -> double
+    {
+      if constexpr (!CHAIN)
+        return (lane < Lt) ? xs_now() : xpre;  // (klo is not needed)
+      else
+      {  // levels [klo, Lt) replayed from the task's root column (a B level: x_0 + z(i) of its sibling state; any
+         // other: roundto(centre)), lanes below klo zero.  The operation sequence of the walk's descents and steps,
+         // so every centre is the walk's.
+        const int tl = here_lane(lane);
+        double Sr    = in.col[ti * 64 + tl];
+        double xr    = (lane >= Lt) ? in.x[ti * 64 + tl] : 0.0;
+        for (int l = Lt - 1; l >= klo; --l)
+        {
+          const double c = rl_f64(Sr, l);
+          double x;
+          if ((B >> l) & 1ull)
+          {
+            const int s_    = rl_i32(st, l);
+            const double x0 = rl_f64(x0s, l);
+            x = x0 + (double)zig_of(ST_IS_SLOW(s_) ? ST_IW(s_) : ST_I(s_), !(rl_f64(cs, l) >= x0));
+          }
+          else
+          {
+            x = rint(c);
+            const double al = x - c;
+            if (fabs(al) == 0.5 && ((al < 0.0) == (c > 0.0)))
+              x = x - (al + al);
+          }
+          xr = (lane == l) ? x : xr;
+          const double ml = ld_row(mu_b, (unsigned)l * MUROW8, lane8);
+          Sr = Sr - (DUAL ? x - c : x) * ml;
+        }
+        if (lane == 0)
+          atomicAdd(&g->replays, 1u);
+        FPHIP_JOIN();
+        return xr;
+      }
+    };
 
-    auto report = [&](double dist, bool &bchg)
+    auto report = [&](double dist, double xleaf, bool &bchg)
     {
       unsigned long long idx = 0;
       if (lane == 0)
@@ -271,7 +345,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
         }
       }
       SolRec *r  = &h->ring[idx % FPHIP_RING_CAP];
-      double xf  = (lane < Lt) ? xs_now() : xpre;
+      const double xf = (CHAIN && lane == 0) ? xleaf : path_x(1);  // (without CHAIN the leaf is lane 0 of x0s)
       const int rl = here_lane(lane);
       r->x[rl]   = (lane < d) ? xf : 0.0;
       {
@@ -303,15 +377,15 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       FPHIP_REFRESH_BOUND(true, bchg);
     };
 
-    // The bound went down: the pending siblings of the hot levels in [klo, Lt) — inside the count n of their
-    // expansion, not visited yet — are tested again, from the last one downwards (the distances are non-decreasing
-    // along the zig-zag); n shrinks past those that fail now: the reference would meet them under the new bound and
-    // turn back (:93).  Lane = level: every lane handles the state of its own level.  (Slow levels test their
-    // siblings one by one anyway.)
+    // The bound went down: the pending siblings of the hot levels (CHAIN: hot B levels) in [klo, Lt) — inside the
+    // count n of their expansion, not visited yet — are tested again, from the last one downwards (the distances are
+    // non-decreasing along the zig-zag); n shrinks past those that fail now: the reference would meet them under the
+    // new bound and turn back (:93).  Lane = level: every lane handles the state of its own level.  CHAIN: a level
+    // left without a sibling loses its P bit.  (Slow levels test their siblings one by one anyway.)
     auto reprune = [&](int klo)
     {
       int s_           = st;
-      const bool act   = lane >= klo && lane < Lt && !ST_IS_SLOW(s_);
+      const bool act   = lane >= klo && lane < Lt && (!CHAIN || ((B >> lane) & 1ull) != 0ull) && !ST_IS_SLOW(s_);
       const double r_l = g->rdiag[lane];
       const double b_l = g->pruning[lane] * maxdist;
       const int cur    = ST_I(s_);
@@ -331,14 +405,14 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       }
       s_ = (s_ & ~(0x7f << 8)) | (n << 8);
       st = act ? s_ : st;
+      if constexpr (CHAIN)
+        P &= ~__builtin_amdgcn_ballot_w64(act && cur + 1 >= n);
       FPHIP_JOIN();
     };
 
-    enum : int { EV_EMIT = 1, EV_DONE = 3, EV_OK = 5, EV_REFRESH = 6, EV_SPECIAL = 7, EV_FAIL = 8, EV_SLOWSTEP = 10 };
+    enum : int { EV_EMIT = 1, EV_DONE = 3, EV_REFRESH = 6, EV_SPECIAL = 7, EV_FAIL = 8, EV_SLOWSTEP = 10 };
     unsigned elo  = (unsigned)donate;
     unsigned erng = 0x7fffffffu;
-    auto hot_range = [&]() {};  // (the special levels are recomputed from elo / zc at the top of the event loop)
-    hot_range();
     bool buffer_full = false;
     bool resume_step = false;
     double par = 0.0, mk = 0.0;
@@ -438,9 +512,24 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               FPHIP_EXIT();
               break;
             }
-            // ---- descend into child 0 (++nodes[kk-1]): S_k is needed again when x[kc] steps to a sibling
-            FPHIP_PUSH(kc < Ts - 1, kc + 1, tri8(kc + 2));
+            // ---- descend into child 0 (++nodes[kk-1])
             const unsigned long long me = lane_bit(kc);
+            if (CHAIN && n == 1)
+            {  // a link of a chain: level kc has no sibling to come back to — nothing of it is stored
+              B &= ~me;
+              cnt32 = add_bit(me, cnt32);
+              nd    = bp_f64(ndj, zero_a);  // lane 0: the child's distance
+              S     = S - (DUAL ? a1 : x1) * mk1;
+              --kc;
+              continue;
+            }
+            // (CHAIN: siblings follow) S_k is needed again when x[kc] steps to a sibling
+            FPHIP_PUSH(kc < Ts - 1, kc + 1, tri8(kc + 2));
+            if constexpr (CHAIN)
+            {
+              P |= me;
+              B |= me;
+            }
             cs    = sel_f64(me, c1, cs);
             x0s   = sel_f64(me, x1, x0s);
             pds   = sel_f64(me, nd, pds);
@@ -454,21 +543,37 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           ka += 4;
           if (ev != EV_FAIL)
             break;  // EV_SPECIAL
-          // no surviving child: the next sibling at level k (at the task root: its marker ends the task)
+          // no surviving child: the next sibling — CHAIN: at the lowest level that has one; else at level k (at the
+          // task root: its marker ends the task)
         }
         at_step = false;
-        // ================= STEP loop: the next child at level k, climbing while levels are exhausted ========
         int tk;
-        for (;;)
+        if constexpr (CHAIN)
         {
-          tk = rl_i32(st, k) + 1;
-          if (__builtin_expect((tk & 0x7f) < ((tk >> 8) & 0x7f), 1))
+          // ================= STEP: the next sibling, at the lowest level of P (every level below is exhausted) ====
+          if (__builtin_expect(P == 0ull, 0))
+          {  // nothing left above the task's root
+            ev = EV_DONE;
             break;
-          ++k;
-          ka += 4;
+          }
+          k  = __builtin_ctzll(P);
+          ka = lane_addr(k);
+          tk = rl_i32(st, k) + 1;
+        }
+        else
+        {
+          // ================= STEP loop: the next child at level k, climbing while levels are exhausted ========
+          for (;;)
+          {
+            tk = rl_i32(st, k) + 1;
+            if (__builtin_expect((tk & 0x7f) < ((tk >> 8) & 0x7f), 1))
+              break;
+            ++k;
+            ka += 4;
+          }
         }
         if (__builtin_expect((tk & 0x7f) >= 64, 0))
-        {  // a slow level, or the task root's marker
+        {  // a slow level (without CHAIN: or the task root's marker)
           ev = EV_SLOWSTEP;
           break;
         }
@@ -477,6 +582,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           ev = EV_REFRESH;
           break;
         }
+        if constexpr (CHAIN)
+          if ((tk & 0x7f) + 1 >= ((tk >> 8) & 0x7f))
+            P &= ~lane_bit(k);  // the last sibling of level k
         {
           // child tk.i of level k: x = x_0 + z(i), its distance (:91-92), the column of its node (:104-110)
           v2u qk = r_issue(rptab, (unsigned)k * MUROW8);
@@ -542,9 +650,12 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             cnt += (lane == 0) ? 1ull : 0ull;
             if (__builtin_amdgcn_ballot_w64(ndc > 0.0) != 0ull)
             {
-              x0s = (lane == 0) ? x : x0s;
-              cs  = (lane == 0) ? x : cs;
-              report(ndc, bchg);
+              if constexpr (!CHAIN)
+              {  // (the leaf's coefficient reaches the record through lane 0 of the level registers)
+                x0s = (lane == 0) ? x : x0s;
+                cs  = (lane == 0) ? x : cs;
+              }
+              report(ndc, x, bchg);
               FPHIP_JOIN();
             }
             if (zig)
@@ -567,10 +678,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           // for no reason any more.  Only the first child is established here; its siblings are the slow step's.
           const bool nz = __builtin_amdgcn_ballot_w64(nd != 0.0) != 0ull;
           if (zc && nz)
-          {
-            zc = false;
-            hot_range();
-          }
+            zc = false;  // (the special levels are recomputed from elo / zc at the top of the event loop)
           kc              = k - 1;
           const double rk = g->rdiag[kc], pk = g->pruning[kc];
           if constexpr (MU_LDS)
@@ -592,6 +700,11 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             continue;
           }
           FPHIP_PUSH(k < Ts, k, tri8(k + 1));
+          if constexpr (CHAIN)
+          {
+            P |= lane_bit(kc);
+            B |= lane_bit(kc);
+          }
           cs  = (lane == kc) ? c1 : cs;
           x0s = (lane == kc) ? x1 : x0s;
           pds = (lane == kc) ? nd : pds;
@@ -604,9 +717,11 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           continue;  // -> EXPAND at the child
         }
       }
+      if (CHAIN && ev == EV_DONE)
+        break;
       if (ev == EV_SLOWSTEP)
       {
-        if (k >= Lt)
+        if (!CHAIN && k >= Lt)
           break;  // the root's marker: task done
         // the next child of a slow level, one test per child as the reference has it (:80-94): only the odd
         // indices of the zig-zag (x only grows) where the parent's distance is exactly 0
@@ -622,9 +737,14 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
         const double ndn = pk + a * a * rk;
         const bool ok    = nxt < 32760 && __builtin_amdgcn_ballot_w64(ndn <= pr * maxdist) != 0ull;
         if (!ok)
-        {  // exhausted: the level above steps
-          st = (lane == k) ? 0 : st;
-          ++k;
+        {  // exhausted: a level above steps
+          if constexpr (CHAIN)
+            P &= ~lane_bit(k);
+          else
+          {
+            st = (lane == k) ? 0 : st;
+            ++k;
+          }
           resume_step = true;
           FPHIP_JOIN();
           continue;
@@ -647,7 +767,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
         {
           const int el                              = here_lane(lane);
           out.col[(unsigned long long)oi * 64 + el] = S;
-          const double xf                           = (lane < Lt) ? xs_now() : xpre;
+          const double xf                           = path_x(k);
           out.x[(unsigned long long)oi * 64 + el]   = xf;
           if (lane == 0)
           {
@@ -666,7 +786,6 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           donate      = 1 << 20;
           elo         = 1u << 20;
           erng        = 0u;
-          hot_range();
           continue;
         }
       }
@@ -694,7 +813,6 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           }
         }
         FPHIP_JOIN();
-        hot_range();
       }
       resume_step = true;
     }
@@ -711,15 +829,19 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
     atomicAdd(&g->iters, (unsigned long long)iter);
 }
 
-#define FPHIP_INST(M, D)                                                                                \
-  template __global__ void enum_walk_kernel<M, D>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int,   \
+#define FPHIP_INST(M, D, C)                                                                             \
+  template __global__ void enum_walk_kernel<M, D, C>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int, \
                                                   unsigned, unsigned, const unsigned *, int, int,       \
                                                   unsigned, const double *, double *, int, unsigned *,   \
                                                   const unsigned *, unsigned, unsigned long long);
-FPHIP_INST(true, false)
-FPHIP_INST(false, false)
-FPHIP_INST(true, true)
-FPHIP_INST(false, true)
+FPHIP_INST(true, false, false)
+FPHIP_INST(false, false, false)
+FPHIP_INST(true, true, false)
+FPHIP_INST(false, true, false)
+FPHIP_INST(true, false, true)
+FPHIP_INST(false, false, true)
+FPHIP_INST(true, true, true)
+FPHIP_INST(false, true, true)
 #undef FPHIP_INST
 
 }  // namespace fphip

@@ -1,4 +1,4 @@
-"""The third-generation walk (enum_chain_kernel, enum_walk3.hip) next to the second (enum_walk_kernel, FPHIP_WALK3=0):
+"""The third-generation walk (enum_walk_kernel<.., CHAIN = true>, enum_walk.hip) next to the second (<.., false>, FPHIP_WALK3=0):
 each run is checked on its own against the reference's golden vectors or the C oracle.  The chain walk stores nothing
 for a node with one child and replays the path from the task's root column where coefficients are needed — the
 level-1 leaf reports (the candidate lists below), the prefixes of donated tasks (a small FPHIP_BUDGET), reprune
