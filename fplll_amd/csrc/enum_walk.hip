@@ -518,7 +518,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             {  // a link of a chain: level kc has no sibling to come back to — nothing of it is stored
               B &= ~me;
               cnt32 = add_bit(me, cnt32);
-              nd    = bp_f64(ndj, zero_a);  // lane 0: the child's distance
+              nd    = nd + a1 * a1 * rp_r(q1);  // the child's distance (lane 0's ndj: z = 0), in every lane's own registers
               S     = S - (DUAL ? a1 : x1) * mk1;
               --kc;
               continue;
@@ -535,7 +535,10 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             pds   = sel_f64(me, nd, pds);
             st    = wl_i32(n << 8, kc, st);
             cnt32 = add_bit(me, cnt32);
-            nd    = bp_f64(ndj, zero_a);  // lane 0: the first child's distance
+            if constexpr (CHAIN)
+              nd = nd + a1 * a1 * rp_r(q1);  // the first child's distance, as in the chain descent
+            else
+              nd = bp_f64(ndj, zero_a);  // lane 0: the first child's distance
             S     = S - (DUAL ? a1 : x1) * mk1;
             --kc;
           }

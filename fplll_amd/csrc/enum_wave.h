@@ -22,6 +22,9 @@ __device__ __forceinline__ int rl_i32(int v, int lane) { return __builtin_amdgcn
 // The same value through the LDS crossbar (ds_bpermute_b32: every lane reads lane `addr4 / 4`; no LDS
 // memory involved): v_readlane_b32 occupies the vector ALU for TWO issue slots (measured:
 // tests/perf/micro/valu_rates.hip), and the walk is bound by exactly that port while the LDS port idles.
+// (True of round 3's walk at 40 VALU per node.  Since the third generation, at 18 VALU per node, the kernel is
+// bound by the LDS unit the four SIMDs of a CU share: every ds_bpermute_b32 per node costs node time, and a
+// value every lane can compute from its own registers does not go through here — DESIGN.md section 3.)
 // The result sits in a VGPR (wave-uniform in value, lane-varying for the compiler): fine where it feeds
 // vector arithmetic; conditions derived from it go through a ballot.
 __device__ __forceinline__ int bp_i32(int v, int addr4) { return __builtin_amdgcn_ds_bpermute(addr4, v); }
