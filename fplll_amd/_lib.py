@@ -42,6 +42,7 @@ class EnumOpts(ctypes.Structure):
         ("min_nodes_decline", ctypes.c_int),
         ("gather", GATHER_CB),
         ("gather_user", ctypes.c_void_p),
+        ("ordered", ctypes.c_int),
     ]
 
 
@@ -58,6 +59,8 @@ class EnumStats(ctypes.Structure):
         ("overflowed", ctypes.c_int),
         ("bfs_restarts", ctypes.c_int),
         ("moved_tasks", ctypes.c_uint64),
+        ("windows", ctypes.c_int),
+        ("candidates", ctypes.c_uint64),
     ]
 
 
@@ -88,6 +91,12 @@ def load():
         vp, vp, ctypes.POINTER(EnumStats)
     ]
     lib.fphip_enum_run.restype = ctypes.c_int
+    # host half of the reference-order mode (include/fplll_hip_debug.h): needs no device
+    lib.fphip_debug_order_key.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp]
+    lib.fphip_debug_order_key.restype = ctypes.c_int
+    lib.fphip_debug_order_replay.argtypes = [ctypes.c_int, ctypes.c_double, vp, vp, vp, ctypes.c_int, vp, vp, SOL_CB,
+                                             vp, ctypes.POINTER(ctypes.c_double)]
+    lib.fphip_debug_order_replay.restype = ctypes.c_int
     _lib = lib
     return lib
 

@@ -21,6 +21,7 @@
 #include "dev_mem.h"
 #include "trace.h"
 #include "enum_device.h"
+#include "enum_order.h"
 
 
 namespace fphip
@@ -47,6 +48,10 @@ __global__ void enum_walk_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf o
 size_t deal_work_bytes(unsigned n);
 unsigned deal_tasks_device(hipStream_t s, const unsigned long long *keys, const double *pd, const unsigned *slot_of,
                            unsigned n, unsigned W, unsigned rank, unsigned *mine, void *work, size_t work_bytes);
+// enum_order.hip: the final task list in the reference's depth-first order (ordered calls)
+size_t order_work_bytes(unsigned n);
+int order_tasks_device(hipStream_t s, const DevShared *g, TaskBuf in, unsigned n, int d, const unsigned *slots,
+                       unsigned *list, void *work, size_t work_bytes, int num_cus, int *sort_passes);
 __global__ void task_pack_kernel(TaskBuf in, unsigned lo, unsigned n, double *rec, const double *xhi_root, int xstr);
 __global__ void task_unpack_kernel(TaskBuf out, unsigned lo, unsigned n, const double *rec, double *xhi_root, int xstr,
                                    unsigned root_base);
@@ -146,6 +151,9 @@ struct fphip_ctx
   unsigned *idxlist            = nullptr;  // device: this rank's task indices, heaviest first
   void *deal_work              = nullptr;  // device: scratch of the device-side deal (enum_deal.hip)
   size_t deal_work_bytes       = 0;
+  void *order_work             = nullptr;  // device: scratch of the depth-first ordering of the tasks (enum_order.hip)
+  size_t order_work_bytes      = 0;
+  int ordered_running          = 0;        // an ordered call is in flight: fphip_enum_lower_bound is ignored
   double *xhi_root             = nullptr;  // device: cap * 64 doubles: the coefficients of levels >= 64 per level-64
                                            // ancestor (blocks larger than 64; 64 doubles per started chunk of levels)
   QueueMem *qm                 = nullptr;  // device: ticket / emission counters of the current call
@@ -185,7 +193,7 @@ static int fail(fphip_ctx *ctx, const char *fmt, ...)
       return fail(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" int fphip_abi_version(void) { return 1; }
+extern "C" int fphip_abi_version(void) { return 2; }
 
 extern "C" int fphip_device_count(void)
 {
@@ -355,6 +363,8 @@ extern "C" void fphip_destroy(fphip_ctx *ctx)
     fphip_dev_free(ctx->idxlist, ctx->stream);
   if (ctx->deal_work)
     fphip_dev_free(ctx->deal_work, ctx->stream);
+  if (ctx->order_work)
+    fphip_dev_free(ctx->order_work, ctx->stream);
   if (ctx->g)
     fphip_dev_free(ctx->g, ctx->stream);
   // Wait for the stream BEFORE the pinned buffers go back to the process-wide cache: after an error
@@ -439,6 +449,10 @@ extern "C" int fphip_enum_lower_bound(fphip_ctx *ctx, double bound)
 {
   if (!ctx || !ctx->h)
     return FPHIP_ERROR;
+  // an ordered call only ever runs under bounds it has committed itself: a foreign bound could cut a node the
+  // reference visits
+  if (__atomic_load_n(&ctx->ordered_running, __ATOMIC_ACQUIRE))
+    return FPHIP_OK;
   publish_bound_min(ctx, bound);
   return FPHIP_OK;
 }
@@ -632,6 +646,131 @@ static int rebalance_tasks(fphip_ctx *ctx, const fphip_enum_opts &o, TaskBuf buf
   return FPHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reference-order mode (fphip_enum_opts::ordered): the candidate store and the replay.
+//
+// The device walks a SUPERSET of the reference's tree — every launch runs under a bound the reference had not yet
+// gone below at that point of its walk — and the ring consumer only stores what it reports.  The replay then takes
+// the stored candidates in the reference's depth-first order (enum_order.h) and decides, with the radius history it
+// rebuilds on the way, which of them the reference visits: those are handed to the caller's callback, in that order.
+//   A candidate c is visited iff every level at or below the highest level where c differs from the last candidate
+// p that went to the callback passes nd_k(c) <= pruning_k * B: the levels c shares with p were entered before the
+// bound dropped to B and are not tested again (enumerate_base.cpp:74-94 — a bound only acts on the NEXT test of a
+// level); the siblings between p's and c's coefficient at the level where they part are closer to the centre than
+// c's, so they pass if c's does.
+// ---------------------------------------------------------------------------------------------
+namespace
+{
+struct OrderCand
+{
+  double dist;
+  std::vector<double> x;       // d coefficients
+  std::vector<unsigned> rank;  // d ranks
+  std::vector<double> nd;      // d partial distances (nd[k] includes level k)
+};
+
+struct OrderReplay
+{
+  int d = 0;
+  const double *mut = nullptr, *rdiag = nullptr;
+  double prun[FPHIP_ENUM_MAX_DIM];
+  double B = 0.0;
+  bool have_p = false;
+  std::vector<double> px;
+  std::vector<OrderCand> pending;
+  uint64_t stored = 0, delivered = 0, mismatched = 0;
+
+  void init(int d_, const double *mut_, const double *rdiag_, const double *pruning, double maxdist)
+  {
+    d     = d_;
+    mut   = mut_;
+    rdiag = rdiag_;
+    for (int k = 0; k < d; ++k)
+      prun[k] = pruning ? pruning[k] : 1.0;
+    B = maxdist;
+  }
+  void add(double dist, const double *x)
+  {
+    OrderCand c;
+    c.dist = dist;
+    c.x.assign(x, x + d);
+    c.rank.resize(d);
+    c.nd.resize(d);
+    order_vector(d, mut, rdiag, c.x.data(), 0, c.rank.data(), c.nd.data());
+    if (memcmp(&c.nd[0], &dist, sizeof(double)) != 0)
+      ++mismatched;  // (the device's distance is the reference's sum: anything else is a defect)
+    pending.push_back(std::move(c));
+    ++stored;
+  }
+  // replay the stored candidates in front of `frontier` (ranks of the first subtree not walked yet; null: all)
+  void commit(const unsigned *frontier, fphip_sol_cb cb, void *user)
+  {
+    std::vector<OrderCand> now, later;
+    for (OrderCand &c : pending)
+      ((!frontier || order_before(d, c.rank.data(), frontier)) ? now : later).push_back(std::move(c));
+    pending.swap(later);
+    std::stable_sort(now.begin(), now.end(), [&](const OrderCand &a, const OrderCand &b)
+                     { return order_before(d, a.rank.data(), b.rank.data()); });
+    for (OrderCand &c : now)
+    {
+      if (!(B > 0.0))
+        break;  // the evaluator stopped the enumeration
+      int h = d - 1;
+      if (have_p)
+        while (h > 0 && c.x[h] == px[h])
+          --h;
+      bool visited = true;
+      for (int k = h; k >= 0 && visited; --k)
+        visited = c.nd[k] <= prun[k] * B;
+      if (!visited || !(c.nd[0] > 0.0))
+        continue;
+      const double nb = cb(user, c.dist, c.x.data());
+      ++delivered;
+      // (the reference's evaluators only ever shrink the bound; the superset was walked under B, so it cannot grow)
+      B = (nb >= 0.0) ? std::min(B, nb) : 0.0;
+      px     = c.x;
+      have_p = true;
+    }
+    if (!(B > 0.0))
+      pending.clear();
+  }
+};
+
+// what the ring consumer calls instead of the caller's callback: store, leave the bound alone
+double order_collect_cb(void *user, double dist, const double *x)
+{
+  static_cast<OrderReplay *>(user)->add(dist, x);
+  return HUGE_VAL;
+}
+}  // namespace
+
+// host-only entries of the CPU suite (include/fplll_hip_debug.h)
+extern "C" int fphip_debug_order_key(int dim, const double *mut, const double *rdiag, const double *x, unsigned *rank_out,
+                                     double *nd_out)
+{
+  if (dim < 1 || dim > FPHIP_ENUM_MAX_DIM || !mut || !rdiag || !x || !rank_out)
+    return FPHIP_ERROR;
+  order_vector(dim, mut, rdiag, x, 0, rank_out, nd_out);
+  return FPHIP_OK;
+}
+extern "C" int fphip_debug_order_replay(int dim, double maxdist, const double *mut, const double *rdiag,
+                                        const double *pruning, int n, const double *dist, const double *x, fphip_sol_cb cb,
+                                        void *user, double *final_bound)
+{
+  if (dim < 1 || dim > FPHIP_ENUM_MAX_DIM || !mut || !rdiag || n < 0 || (n > 0 && (!dist || !x)) || !cb)
+    return FPHIP_ERROR;
+  OrderReplay rp;
+  rp.init(dim, mut, rdiag, pruning, maxdist);
+  for (int i = 0; i < n; ++i)
+    rp.add(dist[i], x + (size_t)i * dim);
+  if (rp.mismatched)
+    return FPHIP_ERROR;
+  rp.commit(nullptr, cb, user);
+  if (final_bound)
+    *final_bound = rp.B;
+  return (int)rp.delivered;
+}
+
 extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const double *mut,
                               const double *rdiag, const double *pruning,
                               const fphip_enum_opts *opts_in, fphip_sol_cb cb,
@@ -667,6 +806,16 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
   if (dual && o.findsubsols)
     return FPHIP_UNSUPPORTED;
   const bool subs = o.findsubsols != 0;
+  // reference-order mode, v1: primal, no sub-solutions, one chunk of levels, one rank
+  const bool ordered = o.ordered != 0;
+  // (a bound exchange between ranks is declined with them: the bound it would publish is a foreign one, the same
+  //  hazard fphip_enum_lower_bound is ignored for)
+  if (ordered && (dual || subs || d > 64 || o.shard_count > 1 || o.exchange))
+  {
+    snprintf(ctx->err, sizeof ctx->err,
+             "ordered enumeration: not with dual, findsubsols, more than 64 rows, several ranks or a bound exchange");
+    return FPHIP_UNSUPPORTED;
+  }
   if (!(maxdist >= 0.0))
     return FPHIP_UNSUPPORTED;
   for (int i = 0; i < d; ++i)
@@ -713,6 +862,28 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
   // call whose expansion overflowed a buffer starts over with them.
   bool use_bfs = env_int("FPHIP_BFS", 1) != 0 && !subs;
   int bfs_restarts = 0;
+  // ordered: the ring consumer stores the candidates, the caller's callback is only called by the replay
+  OrderReplay ost;
+  fphip_sol_cb cb_dev = cb;
+  void *user_dev      = user;
+  struct OrderedFlag
+  {
+    int *p;
+    ~OrderedFlag()
+    {
+      if (p)
+        __atomic_store_n(p, 0, __ATOMIC_RELEASE);
+    }
+  } ordered_flag{nullptr};
+  int windows = 0, order_passes = 0;
+  if (ordered)
+  {
+    ost.init(d, mut, rdiag, pruning, maxdist);
+    cb_dev  = order_collect_cb;
+    user_dev = &ost;
+    __atomic_store_n(&ctx->ordered_running, 1, __ATOMIC_RELEASE);
+    ordered_flag.p = &ctx->ordered_running;
+  }
 restart:
   // ---- upload the block: rdiag, pruning, mu rows (triangular) ---------------------------------
   DevShared *st = ctx->stage;
@@ -1005,7 +1176,7 @@ restart:
     const unsigned bgrid = std::max(32u, ((unsigned)ctx->num_cus * (unsigned)env_int("FPHIP_BFS_WG_PER_CU", 1)) / 32u * 32u);
     while (Lv > Lend)
       bfs_launch(1, bgrid, 256u);
-    const bool want_slots = o.shard_count > 1 && !bfs_sharded;
+    const bool want_slots = (o.shard_count > 1 && !bfs_sharded) || ordered;
     hipLaunchKernelGGL(enum_bfs_epilogue, dim3(1), dim3(1024), 0, ctx->stream, ctx->g, ctx->h, ctx->qm, rcap,
                        want_slots ? ctx->slots : nullptr, want_slots ? ctx->pdc : nullptr, ctx->buf[0].pd);
     HIPCHK(ctx, hipGetLastError());
@@ -1121,7 +1292,10 @@ restart:
     // only the first final round is sharded across GPUs; donated tasks stay on their GPU
     const bool shard_now = in_final && round == 0 && o.shard_count > 1 && !bfs_sharded;
     // (a regioned task list that is not dealt over ranks is drawn region by region: one launch)
-    const int chunks     = (in_final && round == 0 && !(regioned && !shard_now)) ? o.exchange_chunks : 1;
+    // ordered: the first (and only: no donation) walk round goes over the task list sorted into the reference's
+    // depth-first order, in windows
+    const bool order_now = ordered && in_final && round == 0;
+    const int chunks     = (in_final && round == 0 && !(regioned && !shard_now) && !order_now) ? o.exchange_chunks : 1;
     const unsigned *idxl = nullptr;
     unsigned n_list      = C;  // number of tasks this rank walks in this round
     if (shard_now)
@@ -1198,13 +1372,101 @@ restart:
       idxl = ctx->idxlist;
       }
     }
+    std::vector<unsigned> cuts, order_host;  // ordered: the window boundaries, the sorted list on the host
+    std::vector<double> task_x;              // ... and, where the host ordered the list, its copy of the task records
+    std::vector<int> task_level;
+    if (ordered && in_final && round > 0)
+      return fail(ctx, "internal: an ordered call donated tasks");
+    if (order_now)
+    {
+      FPHIP_RANGE("enum: depth-first order of the tasks");
+      if (regioned && n_slots != C)
+        return fail(ctx, "internal: regioned task list without its slot list in an ordered call");
+      const unsigned *slots = regioned ? ctx->slots : nullptr;
+      const size_t need     = order_work_bytes(C);
+      if (ctx->order_work_bytes < need)
+      {
+        if (ctx->order_work)
+          fphip_dev_free(ctx->order_work, ctx->stream);
+        ctx->order_work       = nullptr;
+        ctx->order_work_bytes = 0;
+        HIPCHK(ctx, fphip_dev_alloc(&ctx->order_work, need, ctx->stream));
+        ctx->order_work_bytes = need;
+      }
+      const int rco = order_tasks_device(ctx->stream, ctx->g, ctx->buf[cur], C, d, slots, ctx->idxlist, ctx->order_work,
+                                         ctx->order_work_bytes, ctx->num_cus, &order_passes);
+      if (rco < 0)
+        return fail(ctx, "the device-side ordering of the task list failed");
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      order_host.resize(C);
+      if (rco == 1)
+      {
+        // a rank beyond a key byte (a node with more than 127 children above the tasks' roots): this call's list is
+        // ordered on the host with the same comparator, from the tasks' coefficients (one copy of the slots in use; the
+        // window loop reads its frontier tasks from the same copy)
+        std::vector<unsigned> where(C);
+        if (slots)
+          HIPCHK(ctx, hipMemcpy(where.data(), slots, (size_t)C * 4, hipMemcpyDeviceToHost));
+        else
+          for (unsigned i = 0; i < C; ++i)
+            where[i] = i;
+        const unsigned span = *std::max_element(where.begin(), where.end()) + 1u;
+        if (span > ctx->cap)
+          return fail(ctx, "internal: a task slot beyond the task buffer in an ordered call");
+        task_x.resize((size_t)span * 64);
+        task_level.resize(span);
+        HIPCHK(ctx, hipMemcpy(task_x.data(), ctx->buf[cur].x, (size_t)span * 64 * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(task_level.data(), ctx->buf[cur].level, (size_t)span * sizeof(int), hipMemcpyDeviceToHost));
+        std::vector<unsigned> ranks((size_t)C * d);
+        for (unsigned i = 0; i < C; ++i)
+          order_vector(d, mut, rdiag, &task_x[(size_t)where[i] * 64], task_level[where[i]], &ranks[(size_t)i * d], nullptr);
+        std::vector<unsigned> perm(C);
+        for (unsigned i = 0; i < C; ++i)
+          perm[i] = i;
+        std::stable_sort(perm.begin(), perm.end(), [&](unsigned a, unsigned b)
+                         { return order_before(d, &ranks[(size_t)a * d], &ranks[(size_t)b * d]); });
+        for (unsigned i = 0; i < C; ++i)
+          order_host[i] = where[perm[i]];
+        HIPCHK(ctx, hipMemcpy(ctx->idxlist, order_host.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+        order_passes = -1;
+      }
+      else
+        HIPCHK(ctx, hipMemcpy(order_host.data(), ctx->idxlist, (size_t)C * 4, hipMemcpyDeviceToHost));
+      idxl = ctx->idxlist;
+      if (debug)
+        fprintf(stderr, "[fphip] ordered: %u tasks sorted %s (%d radix passes)\n", C,
+                order_passes < 0 ? "on the host" : "on the device", order_passes);
+      // Window schedule: FPHIP_ORDER_WINDOWS = "first[,growth]" — the first window takes `first` tasks (0: the whole
+      // list in one window), every further one `growth` times the one before.  Small first windows: the reference's
+      // first solutions sit at the front of its walk and prune everything behind them.
+      unsigned first = 1024;
+      double grow    = 8.0;
+      if (const char *ws = getenv("FPHIP_ORDER_WINDOWS"))
+        if (*ws)
+        {
+          double g2 = 0.0;
+          const int got = sscanf(ws, "%u,%lf", &first, &g2);
+          if (got >= 2 && g2 >= 1.0)
+            grow = g2;
+        }
+      cuts.push_back(0u);
+      double wsz = (double)first;
+      while (cuts.back() < C)
+      {
+        const bool last = first == 0u || cuts.size() > 128u || launch_idx + (int)cuts.size() + 1 >= FPHIP_MAX_LAUNCHES;
+        const double nxtcut = last ? (double)C : std::min((double)C, (double)cuts.back() + std::max(1.0, wsz));
+        cuts.push_back((unsigned)nxtcut);
+        wsz *= grow;
+      }
+    }
     const int count_nodes = (in_final || o.shard_index == 0) ? 1 : 0;
     HIPCHK(ctx, hipMemsetAsync(ctx->buf[nxt].count, 0, 4, ctx->stream));
 
-    for (int ch = 0; ch < chunks; ++ch)
+    const int nchunk = order_now ? (int)cuts.size() - 1 : chunks;
+    for (int ch = 0; ch < nchunk; ++ch)
     {
-      unsigned lo = (unsigned)(((unsigned long long)n_list * ch) / chunks);
-      unsigned hi = (unsigned)(((unsigned long long)n_list * (ch + 1)) / chunks);
+      unsigned lo = order_now ? cuts[ch] : (unsigned)(((unsigned long long)n_list * ch) / chunks);
+      unsigned hi = order_now ? cuts[ch + 1] : (unsigned)(((unsigned long long)n_list * (ch + 1)) / chunks);
       if (hi <= lo && !(in_final && o.exchange))
         continue;
       unsigned mine = hi - lo;
@@ -1220,12 +1482,14 @@ restart:
         HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
         // (FPHIP_SUBS_DONATE=0: sub-solution calls walk without work donation — an A/B switch from the hunt for the
         //  run-to-run differences of the split stack above; donation was not their cause)
-        const unsigned bud = (in_final && round < max_rounds && (!subs || env_int("FPHIP_SUBS_DONATE", 1) != 0)) ? budget : 0u;
+        // (ordered: no donation either — a window is complete when its launch returns)
+        const unsigned bud =
+            (in_final && round < max_rounds && (!subs || env_int("FPHIP_SUBS_DONATE", 1) != 0) && !ordered) ? budget : 0u;
 #define FPHIP_LAUNCH(M, S, D)                                                                       \
   hipLaunchKernelGGL((enum_phase_kernel<M, S, D>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
                      ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, stop, lo, hi, idxl, launch_idx,     \
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],          \
-                     (regioned && !shard_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
+                     (regioned && !shard_now && !order_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
                      (unsigned long long)__atomic_load_n(&ctx->h->bound_bits, __ATOMIC_ACQUIRE))
         // the walk launches (no sub-solutions): the third-generation walk — single-child descents store nothing,
         // the next sibling is one scalar search (enum_walk_kernel<.., CHAIN = true>, enum_walk.hip); FPHIP_WALK3=0
@@ -1234,7 +1498,7 @@ restart:
   hipLaunchKernelGGL((enum_walk_kernel<M, D, C>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
                      ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,           \
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],  \
-                     (regioned && !shard_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
+                     (regioned && !shard_now && !order_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
                      (unsigned long long)__atomic_load_n(&ctx->h->bound_bits, __ATOMIC_ACQUIRE))
 #define FPHIP_LAUNCH2(M, D)                                                                          \
   do                                                                                                 \
@@ -1273,7 +1537,7 @@ restart:
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         ++launch_idx;
-        int rc = wait_serving(ctx, d, cb, subcb, user, &nsol);
+        int rc = wait_serving(ctx, d, cb_dev, subcb, user_dev, &nsol);
         if (rc != FPHIP_OK)
           return rc;
         float ms = 0.f;
@@ -1291,6 +1555,36 @@ restart:
                   o.shard_index, launch_idx - 1, in_final ? "walk" : "split", lo, hi, L, stop,
                   in_final ? budget : 0u, grid, wpb, lds, ms, it);
         }
+      }
+      if (order_now)
+      {
+        // Commit the window: everything in front of the first task of the next window is known now.  The replay hands
+        // the reference's candidates among it to the caller and leaves the bound the reference holds at that
+        // frontier: the next window runs under it.
+        ++windows;
+        if (hi < n_list)
+        {
+          double xr[64];
+          int lv = 0;
+          unsigned fr[64];
+          if (!task_level.empty())
+            order_vector(d, mut, rdiag, &task_x[(size_t)order_host[hi] * 64], task_level[order_host[hi]], fr, nullptr);
+          else
+          {
+            HIPCHK(ctx, hipMemcpy(xr, ctx->buf[cur].x + (size_t)order_host[hi] * 64, sizeof xr, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(&lv, ctx->buf[cur].level + order_host[hi], sizeof lv, hipMemcpyDeviceToHost));
+            order_vector(d, mut, rdiag, xr, lv, fr, nullptr);
+          }
+          ost.commit(fr, cb, user);
+        }
+        else
+          ost.commit(nullptr, cb, user);
+        publish_bound_min(ctx, ost.B);
+        if (debug)
+          fprintf(stderr, "[fphip] ordered window %d [%u,%u): %llu candidates stored, %llu delivered, bound %.17g\n", windows,
+                  lo, hi, (unsigned long long)ost.stored, (unsigned long long)ost.delivered, ost.B);
+        if (!(ost.B > 0.0))
+          break;  // the evaluator stopped the enumeration
       }
       if (in_final && o.exchange && ch + 1 < chunks)
       {  // multi-GPU: agree on the best bound at every chunk boundary (collective: every rank
@@ -1369,6 +1663,15 @@ restart:
     regioned = false;  // what a launch emits is a compact list
   }
   const int phases = launches;
+  if (ordered)
+  {
+    // whatever is still stored (a call without walk launches; candidates of inline-walked overflow subtrees)
+    ost.commit(nullptr, cb, user);
+    if (ost.mismatched)
+      return fail(ctx, "ordered enumeration: %llu candidates whose distance is not the reference's sum",
+                  (unsigned long long)ost.mismatched);
+    nsol = ost.delivered;
+  }
 
   // ---- results --------------------------------------------------------------------------------
   HIPCHK(ctx, hipMemcpy(st, ctx->g, offsetof(DevShared, task_head), hipMemcpyDeviceToHost));
@@ -1396,6 +1699,8 @@ restart:
     stats->overflowed       = (st->error_flags & FPHIP_FLAG_TASK_OVERFLOW) ? 1 : 0;
     stats->bfs_restarts     = bfs_restarts;
     stats->moved_tasks      = moved_tasks;
+    stats->windows          = windows;
+    stats->candidates       = ordered ? ost.stored : nsol;
     stats->wall_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin)
             .count();

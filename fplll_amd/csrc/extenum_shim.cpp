@@ -64,12 +64,14 @@ struct Totals  // FPLLL_HIP_STATS=1: printed when the process exits
 {
   double secs = 0, kernel_ms = 0;
   unsigned long long calls = 0, declined = 0, nodes = 0, moved = 0;
+  unsigned long long ordered = 0, windows = 0, candidates = 0;  // FPLLL_HIP_ORDERED: calls answered in that mode
   ~Totals()
   {
     if (getenv("FPLLL_HIP_STATS") && (calls || declined))
       fprintf(stderr, "[fplll_hip] %llu enumerations on the device (%llu declined): %.3f s in the plugin, "
-                      "%.3f s of kernels, %.3e nodes, %llu subtree tasks moved between devices\n",
-              calls, declined, secs, kernel_ms * 1e-3, (double)nodes, moved);
+                      "%.3f s of kernels, %.3e nodes, %llu subtree tasks moved between devices; "
+                      "%llu in reference-order mode (%llu windows, %llu candidates stored)\n",
+              calls, declined, secs, kernel_ms * 1e-3, (double)nodes, moved, ordered, windows, candidates);
   }
 } g_totals;
 std::mutex g_mutex;  // fplll's global hook is process-wide and unsynchronised (enumerate_ext.cpp:32-37)
@@ -402,7 +404,14 @@ nodes_array_t fplll_hip_extenum(const int dim, enumf maxdist, std::function<cb_s
   const char *mn         = getenv("FPLLL_HIP_MIN_NODES");
   opts.min_nodes_decline = mn ? atoi(mn) : 0;
   opts.findsubsols       = findsubsols ? 1 : 0;
-  if (!multi.empty())
+  // FPLLL_HIP_ORDERED=1: primal calls in reference-order mode (fphip_enum_opts::ordered) — fplll's evaluator sees
+  // its own enumerator's candidates in its own order, so the BASIS of a whole BKZ run is the reference's bit for bit
+  // (the node counts returned to fplll are the device's superset walk, >= the reference's per level).  A call the
+  // mode does not cover (sub-solutions, more than 64 rows) is declined and fplll's enumerator answers it: exact too.
+  // With several devices listed an ordered call runs on the first one (the mode is single-rank).
+  const char *od = getenv("FPLLL_HIP_ORDERED");
+  opts.ordered   = (od && atoi(od) != 0 && !dual) ? 1 : 0;
+  if (!multi.empty() && !opts.ordered)
   {
     const int W = (int)multi.size();
     MultiShared sh;
@@ -497,6 +506,12 @@ nodes_array_t fplll_hip_extenum(const int dim, enumf maxdist, std::function<cb_s
   g_totals.kernel_ms += stats.kernel_ms;
   g_totals.calls++;
   g_totals.nodes += stats.total_nodes;
+  if (opts.ordered && rc == FPHIP_OK)
+  {
+    g_totals.ordered++;
+    g_totals.windows += (unsigned long long)stats.windows;
+    g_totals.candidates += stats.candidates;
+  }
   if (rc != FPHIP_OK)
   {
     // fplll's protocol has one error channel: decline, upon which Enumeration::enumerate runs its

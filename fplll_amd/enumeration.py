@@ -92,7 +92,7 @@ def mut_from_mu(mu):
 def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0, shard_count=1,
                     exchange=None, exchange_chunks=1, target_tasks=0, phase_growth=0,
                     waves_per_block=0, min_nodes_decline=0, dual=False, findsubsols=False,
-                    log=None, gather=None):
+                    log=None, gather=None, ordered=False):
     """Run one SVP enumeration on the GPU through the C ABI.
 
     mut[i*d+j] = mu(j,i) for j>i; rdiag, pruning (or None), maxdist normalised like the reference
@@ -100,7 +100,9 @@ def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0,
     called (serialised) while the kernel runs.  ``exchange(local_bound, local_active) -> (bound,
     any_active)`` is the multi-GPU collective hook (RCCL all-reduce in bench.py); ``gather(block: bytes) ->
     [bytes of rank 0, bytes of rank 1, ...]`` the all-gather the work movement between ranks rides on
-    (fphip_gather_cb: distributed.make_gather).
+    (fphip_gather_cb: distributed.make_gather).  ``ordered=True``: reference-order mode — the evaluator sees exactly
+    the reference's candidates in the reference's order (fphip_enum_opts::ordered); ``res.nodes`` is then the
+    device's work, per level >= the reference's counts.
     """
     lib = ctx.lib
     mut = np.ascontiguousarray(mut, dtype=np.float64)
@@ -171,6 +173,7 @@ def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0,
     opts.waves_per_block = waves_per_block
     opts.min_nodes_decline = min_nodes_decline
     opts.gather = _lib.GATHER_CB(_gc) if gather is not None else _lib.GATHER_CB()
+    opts.ordered = int(bool(ordered))
     nodes = np.zeros(d + 1, dtype=np.uint64)
     stats = _lib.EnumStats()
     rc = lib.fphip_enum_run(ctx.handle, d, ctypes.c_double(maxdist),

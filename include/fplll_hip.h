@@ -122,6 +122,16 @@ typedef struct fphip_enum_opts
    * coefficients of the levels >= 64 (a row of the sender's table of level-64 ancestors). */
   fphip_gather_cb gather;
   void *gather_user;
+  /* 1 → reference-order mode: `cb` receives exactly the candidates fplll's own enumerator would hand its evaluator,
+   * in its order (enumerate_base.cpp's depth-first walk), whatever the evaluator does to the radius — results are
+   * the reference's bit for bit and the same from run to run.  The device walks a superset of the reference's tree
+   * (the task list in depth-first order, in windows; between two windows the host replays the stored candidates
+   * and commits the bound: DESIGN.md "reference-order mode"), so `cb` is called BETWEEN launches, not while one
+   * runs, and fphip_enum_lower_bound is ignored during the call.  nodes_out then counts the device's work: per
+   * level >= the reference's counts.  Declined (FPHIP_UNSUPPORTED) together with dual, findsubsols, dim > 64,
+   * shard_count > 1 or an `exchange` callback (its bound is a foreign one).  FPHIP_ORDER_WINDOWS="first[,growth]" sets the window schedule (default "1024,8"; "0": one
+   * window). */
+  int ordered;
 } fphip_enum_opts;
 
 typedef struct fphip_enum_stats
@@ -137,6 +147,8 @@ typedef struct fphip_enum_stats
   int overflowed; /* task-buffer overflow happened (handled inline, results still exact) */
   int bfs_restarts; /* the breadth-first stage overflowed a buffer and the call started over with split launches */
   uint64_t moved_tasks; /* work movement (fphip_enum_opts::gather): tasks that left or reached this rank */
+  int windows;          /* ordered calls: windows of the task list that were walked (0 otherwise) */
+  uint64_t candidates;  /* candidates the device reported (ordered calls: the superset; `solutions` of them reached cb) */
 } fphip_enum_stats;
 
 /*
@@ -147,6 +159,7 @@ typedef struct fphip_enum_stats
  *   nodes_out[0..dim] : per-level node counts, fplll's counting rule
  *                       (enum/enumerate_base.cpp:31-33 incl. the :181-184 compensation)
  * Level bound = pruning[k]*maxdist; a node survives iff newdist <= bound (NaN-safe form).
+ * With opts->ordered, nodes_out is the device's work (a superset of the reference's walk): per level >= fplll's counts.
  */
 int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const double *mut, const double *rdiag,
                    const double *pruning, const fphip_enum_opts *opts, fphip_sol_cb cb,

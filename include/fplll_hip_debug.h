@@ -34,6 +34,22 @@ int fphip_debug_stream(fphip_ctx *ctx, long long rows, int row_bytes, long long 
 int fphip_debug_dd_op(fphip_ctx *ctx, int op, int count, const double *ahi, const double *alo,
                       const double *bhi, const double *blo, double *ohi, double *olo);
 
+/* Reference-order mode (fphip_enum_opts::ordered), the host half without a device.
+ * fphip_debug_order_key: the depth-first key of a coefficient vector x[0..dim) — rank_out[k] = position of x[k]
+ * among the children of its parent in the reference's walk (zig-zag around the rounded centre, upwards only on
+ * the zero chain), compared lexicographically from level dim-1 down; nd_out (nullable): the partial distances,
+ * nd_out[k] including level k.  mut / rdiag as fphip_enum_run takes them.
+ * fphip_debug_order_replay: the replay over n candidates (dist[i], x[i*dim .. (i+1)*dim)) in ANY order — a superset
+ * of what the reference visits: sorts them by the key, calls cb for exactly those the reference's walk would
+ * report under the radius history cb's return values make, in its order.  Returns the number of cb calls (or
+ * FPHIP_ERROR: bad argument, or a distance that is not the reference's sum for its vector); *final_bound: the
+ * radius at the end. */
+int fphip_debug_order_key(int dim, const double *mut, const double *rdiag, const double *x, unsigned *rank_out,
+                          double *nd_out);
+int fphip_debug_order_replay(int dim, double maxdist, const double *mut, const double *rdiag, const double *pruning,
+                             int n, const double *dist, const double *x, fphip_sol_cb cb, void *user,
+                             double *final_bound);
+
 #ifdef __cplusplus
 }
 #endif
