@@ -7,7 +7,8 @@
 // Hida-Li-Bailey "Library for double-double and quad-double arithmetic", 2007) in libqd's default
 // configuration: "sloppy" addition (QD_IEEE_ADD undefined), the accurate three-step division,
 // Karp's square root, nint by parts.  two_prod uses the hardware FMA (exact product error).  PARITY
-// IS UNPINNED against libqd bit for bit; the kernels are checked against the reference run at 106
+// IS UNPINNED against libqd bit for bit; the arithmetic is checked against mpmath on the host and on the device
+// (tests/test_ftx_cpu.py, tests/test_ftx_gpu.py) and the kernels against the reference run at 106
 // bits of MPFR (the oracle build's FP_NR<mpfr_t>) to double-double accuracy (tests/test_dd_gpu.py).
 #ifndef FPHIP_FTX_H
 #define FPHIP_FTX_H
@@ -147,25 +148,15 @@ template <class FT> __device__ __forceinline__ FT f_rnd_we(FT b, int e)
 __device__ __forceinline__ long long f_to_long(double a, int e) { return (long long)ldexp(a, e); }
 __device__ __forceinline__ long long f_to_long(DD a, int e) { return (long long)ldexp(a.hi, e); }
 
-// an exactly converted 64-bit integer
-__device__ __forceinline__ double f_from_ll(double, long long v) { return (double)v; }
-__device__ __forceinline__ DD f_from_ll(DD, long long v)
-{
-  const double hi = (double)v;  // round to nearest; |v| < 2^63
-  // the remainder is exact in 64-bit arithmetic whenever hi is representable as a long long
-  double lo = 0.0;
-  if (fabs(hi) < 9.2e18)
-    lo = (double)(v - (long long)hi);
-  return DD{hi, lo};
-}
-
 // ---- QD = quad-double (an unevaluated sum of four doubles, ~212 bits): the device stand-in for the reference's
 // FP_NR<qd_real> (fplll/nr/nr_FP_qd.inl over libqd's qd_real), the third stage of the wrapper's ladder
 // (wrapper.cpp:630-710).  Restated from Hida-Li-Bailey (2007) in libqd's default ("sloppy") configuration: addition
 // by component-wise two_sum with a three_sum carry chain, multiplication with the O(eps^3) terms accumulated in
 // plain doubles, division by four quotient corrections, square root by Newton's iteration on 1 / sqrt(a), nint by
 // parts; every result goes through the five-term renormalisation.  Like DD: parity with libqd is UNPINNED bit for
-// bit; the arithmetic is checked against mpmath at quad-double accuracy (tests/test_dd_gpu.py).
+// bit; the arithmetic is checked against mpmath at quad-double accuracy on the host build (tests/test_ftx_cpu.py) and,
+// bit-identical with it, on the device, wave helpers included (tests/test_ftx_gpu.py); the kernels' R, mu and r
+// against exact references at 2^-192 (tests/test_dd_gpu.py).
 struct QD
 {
   double x[4];
@@ -204,7 +195,8 @@ __device__ __forceinline__ QD qd_renorm(double c0, double c1, double c2, double 
   c0 = t.hi;
   c1 = t.lo;
   // ... and one from the top pushes the errors down, skipping zeros (branch-free form: a zero term simply leaves
-  // the running sum where it is; a final pass closes the gaps a skipped zero could have left)
+  // the running sum where it is and claims no output slot, so no gap can open between the components; whatever is
+  // left in `acc` after the last term lands in slot k below)
   double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
   double acc = c0;
   int k      = 0;
@@ -351,11 +343,6 @@ __device__ __forceinline__ QD f_nint(QD a)
   return qd_renorm(x0, x1, x2, x3, 0.0);
 }
 __device__ __forceinline__ long long f_to_long(QD a, int e) { return (long long)ldexp(a.x[0], e); }
-__device__ __forceinline__ QD f_from_ll(QD, long long v)
-{
-  const DD t = f_from_ll(DD{}, v);
-  return QD{{t.hi, t.lo, 0.0, 0.0}};
-}
 
 // wave-level helpers
 __device__ __forceinline__ QD f_shfl_xor(QD v, int m)

@@ -85,10 +85,12 @@ struct LllX
   const int *only_failed;
   int kmin, kstart, kend;
   double delta, eta;
+  int *slot_out;
 };
 template <int NQ, class FT> __global__ void lll_x_kernel(LllX A);
 __global__ void dd_op_kernel(const double *ahi, const double *alo, const double *bhi, const double *blo,
                              double *ohi, double *olo, int op, int count);
+template <class FT> __global__ void ftx_op_kernel(const double *pa, const double *pb, double *po, int op, int count);
 template <int NQ, bool EARLY>
 __global__ void lll_kernel(GsoBatch P, int kmin, int kstart, int kend, double delta, double eta,
                            double logdelta);
@@ -120,6 +122,11 @@ struct fphip_gso
   std::vector<fphip_ctx *> ectx_more;  // … and the further ones of a BATCH of tours (one per hand-off worker)
   double *xbuf;       // lll_x.hip workspace: bf rows [B][d][ldn], then the low planes of mu, r, gf [B][d][ldd] each
   int xbuf_planes = 0;  // ... 3 of them, or 9 once a quad-double run has asked for components 2 and 3
+  // opt-in (fphip_debug_gso_lll_ex_keep) for fphip_debug_gso_lll_ex_plane: the leading planes of mu and r as the
+  // kernel of the last run left them (the getters' mu / r are recomputed in double from the new basis), [B][d][ldd]
+  // each, then the slot of every position, [B][d] ints; x_prec = the precision of that run (0: nothing kept)
+  double *xkeep = nullptr;
+  int x_keep = 0, x_prec = 0;
   // in-loop pruning of the strategy-BKZ service (FPHIP_BKZ_PRUNE_IN_LOOP; fphip_gso_bkz_inloop_pruning)
   double il_preproc = 1e6, il_target = 0.5;
   int il_min_block = 24, il_flags = 0x4 /* PRUNER_GRADIENT */, il_device = 1;
@@ -270,6 +277,8 @@ extern "C" void fphip_gso_destroy(fphip_gso *g)
     fphip_destroy(c);
   if (g->xbuf)
     fphip_dev_free(g->xbuf, fphip_ctx_stream(g->ctx));
+  if (g->xkeep)
+    fphip_dev_free(g->xkeep, fphip_ctx_stream(g->ctx));
   hipStreamSynchronize(fphip_ctx_stream(g->ctx));
   fphip_dev_free(g->P.b, fphip_ctx_stream(g->ctx));
   fphip_dev_free(g->P.bfT, fphip_ctx_stream(g->ctx));
@@ -952,6 +961,16 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
     GCHK(fphip_dev_alloc((void **)&g->xbuf, (n_bf + planes * n_pl) * sizeof(double) + 4096, s));
     g->xbuf_planes = planes;
   }
+  g->x_prec = 0;
+  if (g->x_keep)
+  {  // the slot table starts as the identity: a lattice the kernel skips (only_failed) keeps its rows where they are
+    if (!g->xkeep)
+      GCHK(fphip_dev_alloc((void **)&g->xkeep, (2 * n_pl + B * d) * sizeof(double), s));
+    std::vector<int> ident(B * d);
+    for (size_t i = 0; i < B * d; ++i)
+      ident[i] = (int)(i % d);
+    GCHK(hipMemcpy(g->xkeep + 2 * n_pl, ident.data(), B * d * sizeof(int), hipMemcpyHostToDevice));
+  }
   GCHK(hipMemsetAsync(g->xbuf, 0, (n_bf + planes * n_pl) * sizeof(double), s));
   const bool wide = precision >= 106;
   LllX A;
@@ -982,6 +1001,7 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
   A.kend     = kappa_end;
   A.delta    = delta;
   A.eta      = eta;
+  A.slot_out = g->x_keep ? (int *)(g->xkeep + 2 * n_pl) : nullptr;
   if (d_only_failed)  // the lattices that are skipped keep their rows: b2 := b first
     GCHK(hipMemcpyAsync(g->P.b2, g->P.b, B * d * ldn * sizeof(long long), hipMemcpyDeviceToDevice, s));
   const int need = (g->P.d > g->P.n ? g->P.d : g->P.n);
@@ -1020,6 +1040,12 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
   float ms = 0;
   GCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
   std::swap(g->P.b, g->P.b2);  // the kernel wrote the rows in position order into b2
+  if (g->x_keep)
+  {
+    GCHK(hipMemcpyAsync(g->xkeep, g->P.mu, n_pl * sizeof(double), hipMemcpyDeviceToDevice, s));
+    GCHK(hipMemcpyAsync(g->xkeep + n_pl, g->P.r, n_pl * sizeof(double), hipMemcpyDeviceToDevice, s));
+    g->x_prec = precision;
+  }
   if (status)
     GCHK(hipMemcpy(status, g->P.status, sizeof(int) * B, hipMemcpyDeviceToHost));
   if (info)
@@ -1031,6 +1057,52 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
     rc = launch(g, 0, g->P.d, 0.0, 0);
   g->last_ms = ms;
   return rc;
+}
+
+// mu (which = 0) or r (which = 1) of the last fphip_gso_lll_ex run as lll_x.hip left them, one component plane
+// (0 .. 3) at a time: out[d][d] row-major, rows in POSITION order (the kernel keys them by slot), columns are
+// positions; mu(i,j) for j < i and r(i,j) for j <= i are meaningful, stored like fphip_gso_get_mu / _get_r (row
+// exponents: fphip_gso_get_row_expo).  A plane the run's type does not have reads as zeros.  Needs
+// fphip_debug_gso_lll_ex_keep(g, 1) BEFORE the run (FPHIP_ERROR otherwise): the production path keeps nothing.
+extern "C" int fphip_debug_gso_lll_ex_keep(fphip_gso *g, int on)
+{
+  if (!g)
+    return FPHIP_ERROR;
+  g->x_keep = on != 0;
+  g->x_prec = 0;
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_debug_gso_lll_ex_plane(fphip_gso *g, int lattice, int which, int plane, double *out)
+{
+  if (!g || !out || !g->xbuf || !g->xkeep || g->x_prec == 0 || lattice < 0 || lattice >= g->P.batch || which < 0 || which > 1 ||
+      plane < 0 || plane > 3)
+    return FPHIP_ERROR;
+  const size_t B = (size_t)g->P.batch, d = g->P.d, ldd = g->P.ldd, ldn = g->P.ldn;
+  const size_t n_bf = B * d * ldn, n_pl = B * d * ldd;
+  const int have = g->x_prec == 212 ? 4 : (g->x_prec == 106 ? 2 : 1);
+  if (plane >= have)
+  {
+    memset(out, 0, d * d * sizeof(double));
+    return FPHIP_OK;
+  }
+  // the layout of gso_lll_ex: bf, the low planes of mu / r / gf, two more planes of each (quad-double)
+  const double *tail = g->xkeep;
+  const double *src  = plane == 0 ? tail + which * n_pl
+                       : plane == 1 ? g->xbuf + n_bf + which * n_pl
+                                    : g->xbuf + n_bf + (3 + 2 * which + (plane - 2)) * n_pl;
+  std::vector<double> rows(d * d);
+  std::vector<int> slot(d);
+  GCHK(hipMemcpy2D(rows.data(), d * 8, src + (size_t)lattice * d * ldd, ldd * 8, d * 8, d, hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(slot.data(), (const int *)(tail + 2 * n_pl) + (size_t)lattice * d, d * sizeof(int),
+                 hipMemcpyDeviceToHost));
+  for (size_t p = 0; p < d; ++p)
+  {
+    if (slot[p] < 0 || (size_t)slot[p] >= d)
+      return FPHIP_ERROR;
+    memcpy(out + p * d, rows.data() + (size_t)slot[p] * d, d * sizeof(double));
+  }
+  return FPHIP_OK;
 }
 
 extern "C" int fphip_gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_end, double delta,
@@ -2846,6 +2918,7 @@ struct fphip_hh
   long long *xprevE;
   double *xThi = nullptr, *xTlo = nullptr;  // hlll_x: T of every block of 16 reflectors (blocked application)
   double *xRx = nullptr, *xVx = nullptr;    // hlll_x in quad-double: components 2 and 3 of R and V
+  int x_planes = 0;                         // component planes of R the last fphip_hh_hlll_ex run wrote (0: none yet)
 };
 
 #define HCHK(call)                     \
@@ -3155,6 +3228,7 @@ extern "C" int fphip_hh_hlll(fphip_hh *h, double delta, double eta, double theta
   HCHK(hipEventRecord(h->ev[1], s));
   HCHK(hipStreamSynchronize(s));
   HCHK(hipEventElapsedTime(&h->last_ms, h->ev[0], h->ev[1]));
+  h->x_planes = 1;  // (the double kernel: R has its leading plane only)
   if (status)
     HCHK(hipMemcpy(status, h->P.status, sizeof(int) * B, hipMemcpyDeviceToHost));
   if (info)
@@ -3171,6 +3245,12 @@ static int hh_hlll_ex(fphip_hh *h, double delta, double theta, int precision, co
 {
   if (!h || (precision != 53 && precision != 106 && precision != 212))
     return FPHIP_ERROR;
+  if (precision == 212 && h->P.n > 64)
+  {  // hlll_x_kernel<NQ >= 2, QD>: its one run (n = 72) ended in an illegal memory access whose cause is not found
+    // (DESIGN.md section 4d); until it is, the quad-double type takes one column per lane only
+    snprintf(fphip_ctx_errbuf(h->ctx), 512, "fphip_hh_hlll_ex: precision 212 needs n <= 64 (n = %d)", h->P.n);
+    return FPHIP_ERROR;
+  }
   const size_t B = (size_t)h->P.batch, d = h->P.d, ld = h->P.ldn;
   const bool wide = precision >= 106;  // a low plane of R and V
   if (!h->P.bf)
@@ -3272,6 +3352,7 @@ static int hh_hlll_ex(fphip_hh *h, double delta, double theta, int precision, co
   HCHK(hipEventRecord(h->ev[1], s));
   HCHK(hipStreamSynchronize(s));
   HCHK(hipEventElapsedTime(&h->last_ms, h->ev[0], h->ev[1]));
+  h->x_planes = precision == 212 ? 4 : (precision == 106 ? 2 : 1);
   if (status)
     HCHK(hipMemcpy(status, h->P.status, sizeof(int) * B, hipMemcpyDeviceToHost));
   if (info)
@@ -3394,6 +3475,24 @@ extern "C" int fphip_hh_get_R_lo(fphip_hh *h, int lattice, double *Rlo)
   return FPHIP_OK;
 }
 
+// component plane 0..3 of R after fphip_hh_hlll_ex: R(i,j) = the sum of the planes (0 = fphip_hh_get_R, 1 =
+// fphip_hh_get_R_lo, 2 and 3 the quad-double run's); a plane the last run did not have reads as zeros
+extern "C" int fphip_hh_get_R_plane(fphip_hh *h, int lattice, int plane, double *out)
+{
+  if (!h || !out || h->x_planes == 0 || plane < 0 || plane > 3 || lattice < 0 || lattice >= h->P.batch)
+    return FPHIP_ERROR;
+  if (plane >= h->x_planes)
+  {
+    memset(out, 0, (size_t)h->P.d * h->P.n * 8);
+    return FPHIP_OK;
+  }
+  const size_t pl   = (size_t)h->P.batch * h->P.d * h->P.ldn;  // (Rx: planes 2 and 3 back to back, hlll_x.hip)
+  const double *src = plane == 0 ? h->P.R : (plane == 1 ? h->Rlo : h->xRx + (plane - 2) * pl);
+  HCHK(hipMemcpy2D(out, (size_t)h->P.n * 8, src + (size_t)lattice * h->P.d * h->P.ldn, (size_t)h->P.ldn * 8,
+                   (size_t)h->P.n * 8, h->P.d, hipMemcpyDeviceToHost));
+  return FPHIP_OK;
+}
+
 // double-double arithmetic of the device (ftx.h), element-wise on host arrays — for its unit test
 // against multiprecision.  op: 0 add, 1 sub, 2 mul, 3 div, 4 sqrt(a), 5 nint(a)
 extern "C" int fphip_debug_dd_op(fphip_ctx *ctx, int op, int count, const double *ahi, const double *alo,
@@ -3417,6 +3516,36 @@ extern "C" int fphip_debug_dd_op(fphip_ctx *ctx, int op, int count, const double
   hipMemcpy(olo, dv + 5 * (size_t)count, nb, hipMemcpyDeviceToHost);
   fphip_dev_free(dv, fphip_ctx_stream(ctx));
   return FPHIP_OK;
+}
+
+// either extended type of the device (ftx.h), element-wise and wave-level, on host arrays — for the unit tests against
+// multiprecision and against the host build of the same header.  a, b, out: [comps][count] planes, comps 2 (DD) or
+// 4 (QD); ops as ftx_op_kernel (hlll_x.hip).  The wave-level ops (10..13) take whole wavefronts only.
+extern "C" int fphip_debug_ftx_op(fphip_ctx *ctx, int comps, int op, int count, const double *a, const double *b,
+                                  double *out)
+{
+  if (!ctx || !a || !b || !out || count <= 0 || (comps != 2 && comps != 4) || op < 0 || op > 13 ||
+      (op >= 10 && count % 64 != 0))
+    return FPHIP_ERROR;
+  hipStream_t s    = fphip_ctx_stream(ctx);
+  const size_t npl = (size_t)comps * count, nb = npl * sizeof(double);
+  double *dv       = nullptr;
+  if (fphip_dev_alloc((void **)&dv, 3 * nb, s) != hipSuccess)
+    return FPHIP_ERROR;
+  bool ok = hipMemcpy(dv, a, nb, hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(dv + npl, b, nb, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok)
+  {
+    const dim3 grid((count + 255) / 256), block(256);
+    if (comps == 2)
+      hipLaunchKernelGGL((ftx_op_kernel<DD>), grid, block, 0, s, dv, dv + npl, dv + 2 * npl, op, count);
+    else
+      hipLaunchKernelGGL((ftx_op_kernel<QD>), grid, block, 0, s, dv, dv + npl, dv + 2 * npl, op, count);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
+         hipMemcpy(out, dv + 2 * npl, nb, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  fphip_dev_free(dv, s);
+  return ok ? FPHIP_OK : FPHIP_ERROR;
 }
 
 // R as d×n row-major (only R(i, j<=i) is meaningful, as in the reference); exponents separately

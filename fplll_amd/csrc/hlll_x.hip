@@ -696,4 +696,68 @@ __global__ void dd_op_kernel(const double *ahi, const double *alo, const double 
   olo[i] = r.lo;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Unit-test kernel for ftx.h in either extended type: planes [comps][count] (comps = 2: DD, 4: QD), one element per
+// thread, 256 threads per workgroup.  op 0..5 as dd_op_kernel; 6 f_mul_d(a, b[0]); 7 / 8 f_le / f_gt (1.0 or 0.0 in
+// component 0); 9 f_rnd_we(a, (int)b[0]); the wave-level helpers: 10 f_wave_sum, 11 f_bcast(a, (int)b[0] & 63),
+// 12 f_shfl_up(a, 1), 13 f_shfl_xor(a, (int)b[0] & 63) with a wave-uniform b[0].  For 10..13 the host passes whole
+// wavefronts only (count a multiple of 64), so the bounds check below retires whole waves and no lane leaves
+// before a shuffle.
+// ---------------------------------------------------------------------------------------------
+template <class FT> struct FtxIO;
+template <> struct FtxIO<DD>
+{
+  static __device__ __forceinline__ DD ld(const double *p, size_t cnt, size_t i) { return DD{p[i], p[cnt + i]}; }
+  static __device__ __forceinline__ void st(double *p, size_t cnt, size_t i, DD v)
+  {
+    p[i]       = v.hi;
+    p[cnt + i] = v.lo;
+  }
+};
+template <> struct FtxIO<QD>
+{
+  static __device__ __forceinline__ QD ld(const double *p, size_t cnt, size_t i)
+  {
+    return QD{{p[i], p[cnt + i], p[2 * cnt + i], p[3 * cnt + i]}};
+  }
+  static __device__ __forceinline__ void st(double *p, size_t cnt, size_t i, QD v)
+  {
+    p[i]           = v.x[0];
+    p[cnt + i]     = v.x[1];
+    p[2 * cnt + i] = v.x[2];
+    p[3 * cnt + i] = v.x[3];
+  }
+};
+template <class FT>
+__global__ void __launch_bounds__(256) ftx_op_kernel(const double *pa, const double *pb, double *po, int op, int count)
+{
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, cnt = (size_t)count;
+  if (i >= cnt)
+    return;
+  const FT a = FtxIO<FT>::ld(pa, cnt, i), b = FtxIO<FT>::ld(pb, cnt, i);
+  const double b0 = f_hi(b);
+  FT r = f_from(FT{}, 0.0);
+  switch (op)
+  {
+  case 0: r = f_add(a, b); break;
+  case 1: r = f_sub(a, b); break;
+  case 2: r = f_mul(a, b); break;
+  case 3: r = f_div(a, b); break;
+  case 4: r = f_sqrt(a); break;
+  case 5: r = f_nint(a); break;
+  case 6: r = f_mul_d(a, b0); break;
+  case 7: r = f_from(FT{}, f_le(a, b) ? 1.0 : 0.0); break;
+  case 8: r = f_from(FT{}, f_gt(a, b) ? 1.0 : 0.0); break;
+  case 9: r = f_rnd_we(a, (int)b0); break;
+  case 10: r = f_wave_sum(a); break;
+  case 11: r = f_bcast(a, (int)b0 & 63); break;
+  case 12: r = f_shfl_up(a, 1); break;
+  case 13: r = f_shfl_xor(a, (int)b0 & 63); break;
+  default: break;
+  }
+  FtxIO<FT>::st(po, cnt, i, r);
+}
+template __global__ void ftx_op_kernel<DD>(const double *, const double *, double *, int, int);
+template __global__ void ftx_op_kernel<QD>(const double *, const double *, double *, int, int);
+
 }  // namespace fphip

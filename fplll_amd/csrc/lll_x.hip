@@ -42,6 +42,7 @@ struct LllX
   const int *only_failed; // precision ladder: non-null = only the lattices whose entry is not 1
   int kmin, kstart, kend;
   double delta, eta;
+  int *slot_out;          // null, or [batch][d]: the slot of every position at the end (the key of the rows of mu / r)
 };
 
 template <class FT> struct PlaneX;
@@ -636,6 +637,9 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
           out[(size_t)p * ldn + c] = (c < n) ? b[(size_t)s * ldn + c] : 0;
       }
     }
+    if (A.slot_out)
+      for (int p = lane; p < dT; p += 64)
+        A.slot_out[(size_t)L * dT + p] = slot[p];
     if (lane == 0)
     {
       A.status[L]       = status;

@@ -249,6 +249,27 @@ class MatGSOBatch:
                      st.ctypes.data_as(ctypes.c_void_p), info.ctypes.data_as(ctypes.c_void_p)), "lll_ex")
         return st, info
 
+    def lll_ex_keep(self, on=True):
+        """debug: make lll_ex() keep its own mu / r planes and slot table for lll_ex_plane() (off by default: two
+        more [batch][d][ldd] planes of device memory and two copies per run)"""
+        fn = self.lib.fphip_debug_gso_lll_ex_keep
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self._chk(fn(self.h, int(bool(on))), "lll_ex_keep")
+        self._keep_planes = bool(on)
+
+    def lll_ex_plane(self, lattice, which, plane):
+        """component plane 0..3 of mu (which=0) or r (which=1) as the last lll_ex() run left them in its own
+        arithmetic (the value is the sum of the planes; stored like get_mu_matrix / get_r_matrix, rows by position)"""
+        if not getattr(self, "_keep_planes", False):
+            raise _lib.HipError("lll_ex_plane: call lll_ex_keep(True) before lll_ex()")
+        fn = self.lib.fphip_debug_gso_lll_ex_plane
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        m = np.empty((self.d, self.d), dtype=np.float64)
+        self._chk(fn(self.h, lattice, which, plane, m.ctypes.data_as(ctypes.c_void_p)), "lll_ex_plane")
+        return m
+
     def lll_ladder(self, kappa_min=0, kappa_start=0, kappa_end=-1, delta=LLL_DEF_DELTA, eta=LLL_DEF_ETA):
         """Wrapper::lll's precision ladder on the device (wrapper.cpp:281-359): the exact double kernel,
         then double-double for the lattices that fail in double.  Returns (status, info, stage)."""

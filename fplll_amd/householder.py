@@ -29,6 +29,8 @@ def _bind(lib):
     lib.fphip_hh_hlll_ladder.restype = ctypes.c_int
     lib.fphip_hh_get_R_lo.argtypes = [vp, ctypes.c_int, vp]
     lib.fphip_hh_get_R_lo.restype = ctypes.c_int
+    lib.fphip_hh_get_R_plane.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
+    lib.fphip_hh_get_R_plane.restype = ctypes.c_int
     lib.fphip_hh_get_basis.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
     lib.fphip_hh_hlll.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double, vp, vp]
@@ -129,6 +131,14 @@ class MatHouseholderBatch:
         """low plane of R after hlll(precision=106)"""
         R = np.empty((self.d, self.n))
         self._chk(self.lib.fphip_hh_get_R_lo(self.h, lattice, R.ctypes.data_as(ctypes.c_void_p)), "get_R_lo")
+        return R
+
+    def get_R_plane(self, lattice=0, plane=0):
+        """component plane 0..3 of R after hlll(precision=...): R is the sum of the planes (one at 53 bits, two at
+        106, four at 212; the others read as zeros) times 2^row_expo"""
+        R = np.empty((self.d, self.n))
+        self._chk(self.lib.fphip_hh_get_R_plane(self.h, lattice, int(plane), R.ctypes.data_as(ctypes.c_void_p)),
+                  "get_R_plane")
         return R
 
     def get_R(self, lattice=0):

@@ -537,6 +537,14 @@ int fphip_hh_hlll(fphip_hh *h, double delta, double eta, double theta, double c,
 int fphip_hh_hlll_ex(fphip_hh *h, double delta, double eta, double theta, double c, int precision,
                      int *status, int *info);
 int fphip_hh_get_R_lo(fphip_hh *h, int lattice, double *Rlo);
+/* Component plane 0..3 of R after fphip_hh_hlll_ex, d×n row-major like fphip_hh_get_R: R(i,j) is the sum of the
+ * planes (one at precision 53, two at 106, four at 212); a plane the last run did not have reads as zeros.
+ * Valid directly after fphip_hh_hlll / fphip_hh_hlll_ex only: the other entry points that rewrite R (update_R,
+ * size_reduce, ...) write plane 0 and leave planes 1..3 stale, and after fphip_hh_hlll_ladder the low planes of a
+ * lattice that finished at an earlier stage have been cleared by the later stage.
+ * fphip_hh_hlll_ex at precision 212 takes n <= 64 only and returns FPHIP_ERROR beyond (so does the ladder's third
+ * stage): the kernel instantiations with several columns per lane are unverified in quad-double. */
+int fphip_hh_get_R_plane(fphip_hh *h, int lattice, int plane, double *out);
 /* The precision ladder of the reference's wrapper (hlll_reduction, LM_WRAPPER: wrapper.cpp:478-529 —
  * double first, then the wider types, each stage continuing from the basis the previous one left)
  * with both stages on the device: the exact-order double kernel for the whole batch, then

@@ -33,6 +33,25 @@ int fphip_debug_stream(fphip_ctx *ctx, long long rows, int row_bytes, long long 
  * against multiprecision.  op: 0 add, 1 sub, 2 mul, 3 div, 4 sqrt(a), 5 nint(a). */
 int fphip_debug_dd_op(fphip_ctx *ctx, int op, int count, const double *ahi, const double *alo,
                       const double *bhi, const double *blo, double *ohi, double *olo);
+/* Either extended type of the device (csrc/ftx.h) on host arrays of component planes, a, b, out: [comps][count]
+ * with comps 2 (double-double) or 4 (quad-double).  op 0..5 as above; 6 f_mul_d(a, b[0]); 7 / 8 f_le / f_gt (1.0 or
+ * 0.0 in component 0); 9 f_rnd_we(a, (int)b[0]); wave-level, on wavefronts of 64 consecutive elements (count must be
+ * a multiple of 64, FPHIP_ERROR otherwise): 10 f_wave_sum, 11 f_bcast(a, (int)b[0] & 63), 12 f_shfl_up(a, 1),
+ * 13 f_shfl_xor(a, (int)b[0] & 63) with b[0] the same in the whole wavefront. */
+int fphip_debug_ftx_op(fphip_ctx *ctx, int comps, int op, int count, const double *a, const double *b,
+                       double *out);
+
+/* mu (which = 0) or r (which = 1) of the last fphip_gso_lll_ex run in the arithmetic it ran in, one component plane
+ * (0 .. 3; one plane at precision 53, two at 106, four at 212, the others read as zeros) at a time: the value is the
+ * sum of the planes.  out[d][d] row-major, rows and columns in position order; mu(i,j) for j < i and r(i,j) for
+ * j <= i are meaningful, stored like fphip_gso_get_mu / fphip_gso_get_r (apply fphip_gso_get_row_expo the same way).
+ * (Those getters hand out a GSO recomputed in double from the reduced basis, not these.)
+ * Opt-in: fphip_debug_gso_lll_ex_keep(g, 1) before the run makes fphip_gso_lll_ex keep a copy of the kernel's
+ * leading planes and its slot table (two [batch][d][ldd] planes of device memory and two copies per run, which the
+ * production path does not pay); without it, and after _keep(g, 0), the accessor returns FPHIP_ERROR.  After
+ * fphip_gso_lll_ladder the planes are those of the LAST stage that ran, and only for the lattices it ran on. */
+int fphip_debug_gso_lll_ex_keep(fphip_gso *g, int on);
+int fphip_debug_gso_lll_ex_plane(fphip_gso *g, int lattice, int which, int plane, double *out);
 
 /* Reference-order mode (fphip_enum_opts::ordered), the host half without a device.
  * fphip_debug_order_key: the depth-first key of a coefficient vector x[0..dim) — rank_out[k] = position of x[k]

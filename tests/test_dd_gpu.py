@@ -2,13 +2,18 @@
 
 The reference's FP_NR<dd_real> sits on libqd, an un-vendored optional dependency that is absent here
 (SURVEY.md 8(c)): bit-for-bit parity with it is UNPINNED.  What pins the device path instead:
-  1. the arithmetic of csrc/ftx.h against multiprecision (mpmath) at double-double accuracy;
+  1. the arithmetic of csrc/ftx.h against multiprecision (mpmath) at double-double accuracy (and, for both
+     extended types on every operand class, tests/test_ftx_gpu.py);
   2. the Householder R-factor computed in double-double against the REAL reference run with
      FP_NR<mpfr_t> at 106 bits (tests/golden/hhmp106_*.json.gz, oracle/ref_driver.cpp `hhmp`);
   3. HLLL in double-double: status, a reduced basis of the same lattice, and — where the reference's
      own double / long double / 106-bit runs all agree — the reference's basis
-     (config 5's 256-dim lattice: tests/test_a_configs_at_size_gpu.py)."""
+     (config 5's 256-dim lattice: tests/test_a_configs_at_size_gpu.py).
+The quad-double path (FP_NR<qd_real>'s stand-in) is pinned the same way one level up: its R-factor, and the mu / r of
+lll_x.hip, against EXACT references (the Cholesky factor of the integer Gram matrix, the rational Gram-Schmidt) at
+2^-192."""
 import ctypes
+import functools
 import gzip
 import json
 import os
@@ -18,6 +23,7 @@ import numpy as np
 import pytest
 
 import conftest as C
+import ftx_cases as F
 
 pytestmark = pytest.mark.gpu
 mp = pytest.importorskip("mpmath")
@@ -124,6 +130,88 @@ def test_r_factor_in_double_double_against_mpfr106(ctx, name):
     assert worst[106] <= mp.mpf(2) ** -92   # ~1e-28: double-double accuracy with d*n roundings of slack
     assert worst[53] <= mp.mpf(2) ** -40
     assert worst[106] * 2 ** 30 < worst[53] or worst[53] == 0
+    h.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_r_factor(name):
+    """the basis of hhmp106_<name> and its exact R-factor (ftx_cases.cholesky_rfactor, 700 bits), computed once"""
+    with gzip.open(os.path.join(C.GOLDEN, "hhmp106_%s.json.gz" % name), "rt") as f:
+        j = json.load(f)
+    b = np.array(j["b"], dtype=np.int64).reshape(j["d"], j["n"])
+    return b, F.cholesky_rfactor(b)
+
+
+@pytest.mark.parametrize("name", ["q40"])
+def test_r_factor_at_53_106_212_bits_against_the_exact_cholesky(ctx, name):
+    """What pins the QUAD-double path at quad-double accuracy.  hlll(precision=p) on an already HLLL-reduced basis
+    leaves it alone and ends with its R-factor in R, in p / 53 component planes (fphip_hh_get_R_plane).  The reference
+    is independent of any floating-point run: the lower Cholesky factor of the exact integer Gram matrix at 700 bits
+    (pinned against the reference's MPFR-106 run in tests/test_ftx_cpu.py).  Relative to the row norm:
+      106 bits: 2^-92 (as against MPFR-106 above);
+      212 bits: 2^-192 — the same 12 bits for the d*n roundings under the unit 2^-205 that 2^-92 leaves under 2^-104;
+      and the quad-double run is at least 90 bits better than the double-double one.
+    The planes are really there: components 2 and 3 are non-zero in more than half of the entries, and every entry is
+    a normalised expansion (ftx_cases.normalisation).  A run that computed in double-double and stored zeros, lost a
+    plane, or read one with the wrong stride fails the 2^-192 gate by a hundred bits.
+    hhmp106_q72 is NOT a case here: this test on it (72 columns: two per lane, a kernel instantiation no quad-double
+    run had used before) ended in an illegal memory access on the device inside fphip_hh_hlll_ex, and the cause has not
+    been found.  Until it is, the library refuses quad-double HLLL with n > 64 (the test
+    below), and the case comes back with the fix."""
+    from fplll_amd.householder import MatHouseholderBatch
+    mp.mp.prec = 700
+    b, L = _exact_r_factor(name)
+    d, n = b.shape
+    h = MatHouseholderBatch(ctx, 2, d, n, row_expo=True)
+    worst = {}
+    for prec in (53, 106, 212):
+        h.set_basis(np.stack([b] * 2))
+        st, info = h.hlll(precision=prec)
+        assert list(st) == [1, 1] and int(info[0][0]) == 0 and int(info[1][0]) == 0   # reduced already: no swap
+        assert np.array_equal(h.get_basis(1, 1)[0], b)
+        _, e = h.get_R(1)
+        pl = [h.get_R_plane(1, k) for k in range(4)]
+        for k in range(prec // 53, 4):
+            assert not pl[k].any(), (prec, k)          # planes this type does not have read as zeros
+        w = mp.mpf(0)
+        for i in range(d):
+            rown = mp.sqrt(mp.fsum(t * t for t in L[i]))
+            for jj in range(i + 1):
+                got = mp.fsum(mp.mpf(float(p[i, jj])) for p in pl) * mp.mpf(2) ** int(e[i])
+                w = max(w, abs(got - L[i][jj]) / rown)
+        worst[prec] = w
+        if prec == 212:
+            tri = np.tril_indices(d)
+            ent = np.stack([p[tri] for p in pl], axis=1)
+            bad, above = F.normalisation(ent, 4)
+            assert not bad, bad[:4]
+            nz2, nz3 = np.count_nonzero(ent[:, 2]), np.count_nonzero(ent[:, 3])
+            assert 2 * nz2 > len(ent) and 2 * nz3 > len(ent), (nz2, nz3, len(ent))
+            assert np.array_equal(pl[0], h.get_R(1)[0]) and np.array_equal(pl[1], h.get_R_lo(1))
+    C.note(lambda: ("R-factor %s (%dx%d) vs the exact Cholesky factor, relative to the row norm: 53 bits 2^%.1f, 106 bits "
+                    "2^%.1f, 212 bits 2^%.1f" % ((name, d, n) + tuple(float(mp.log(worst[p], 2)) for p in (53, 106, 212))),))
+    h.close()
+    assert worst[53] <= mp.mpf(2) ** -40
+    assert worst[106] <= mp.mpf(2) ** -92
+    assert worst[212] <= mp.mpf(2) ** -192
+    assert worst[212] * 2 ** 90 < worst[106]
+
+
+def test_quad_double_hlll_refuses_more_than_64_columns(ctx):
+    """fphip_hh_hlll_ex(precision=212) with n > 64 is an error BEFORE anything is launched (see the test above), it
+    says why, and the handle goes on working at the other precisions."""
+    import fplll_amd
+    from fplll_amd.householder import MatHouseholderBatch
+    b, _ = _exact_r_factor("q40")
+    wide = np.zeros((40, 72), dtype=np.int64)
+    wide[:, :40] = b
+    h = MatHouseholderBatch(ctx, 2, 40, 72, row_expo=True)
+    h.set_basis(np.stack([wide] * 2))
+    with pytest.raises(fplll_amd._lib.HipError, match="n <= 64"):
+        h.hlll(precision=212)
+    st, info = h.hlll(precision=106)
+    assert list(st) == [1, 1] and int(info[0][0]) == 0
+    assert np.array_equal(h.get_basis(1, 1)[0], wide)
     h.close()
 
 
@@ -370,6 +458,78 @@ def test_lll_in_quad_double_and_the_three_stage_ladder(ctx, name, monkeypatch):
     out = g.get_basis(0, 8)
     assert all(np.array_equal(out[L], f["b_out"]) for L in range(8))
     g.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_gso(name):
+    """the reference's output basis of an LLL fixture and its exact rational Gram-Schmidt, as mpf at 700 bits"""
+    f = C.load_lll_fixture(os.path.join(C.GOLDEN, name + ".json"))
+    b = f["b_out"]
+    mu, r = F.exact_gso(b)
+    mp.mp.prec = 700
+    q = lambda x: mp.mpf(x.numerator) / mp.mpf(x.denominator)  # noqa: E731
+    return f, b, [[q(x) for x in row] for row in mu], [[q(x) for x in row] for row in r]
+
+
+@pytest.mark.parametrize("name", ["lll_q40", "lll_u24"])
+def test_lll_mu_and_r_at_53_106_212_bits_against_exact_gram_schmidt(ctx, name):
+    """lll_x.hip at quad-double accuracy: fphip_gso_lll_ex(precision=p) on an already LLL-reduced basis (the
+    reference's output) swaps nothing and ends with the Gram-Schmidt coefficients of that basis in its own arithmetic,
+    in p / 53 component planes (fphip_debug_gso_lll_ex_plane: rows back in position order).  Reference: exact rational
+    Gram-Schmidt (fractions).  mu(i,j) relative to max(1, |mu|), r(i,j), j <= i, relative to r(i,i): the gates of the
+    R-factor test — 2^-92 at 106 bits, 2^-192 at 212, the quad-double run 90 bits better than the double-double one —
+    and components 2 and 3 non-zero in more than half of the entries, every entry normalised.  (The off-diagonal r
+    relative to |b_i| |b_j|, the bound of every term of its recurrence, is printed beside it.)"""
+    from fplll_amd.gso import MatGSOBatch
+    f, b, mu, r = _exact_gso(name)
+    mp.mp.prec = 700
+    d = f["d"]
+    norm = [mp.sqrt(mp.mpf(int(np.dot(row.astype(object), row.astype(object))))) for row in b]
+    g = MatGSOBatch(ctx, 2, f["d"], f["n"])
+    import fplll_amd
+    with pytest.raises(fplll_amd._lib.HipError):
+        g.lll_ex_plane(1, 0, 0)       # nothing is kept unless asked for
+    g.lll_ex_keep(True)
+    worst, worst_bb = {}, {}
+    for prec in (53, 106, 212):
+        g.set_basis(np.stack([b] * 2))
+        st, info = g.lll_ex(prec, 0, 0, -1, f["delta"], f["eta"])
+        assert list(st) == [1, 1] and int(info[0][1]) == 0 and int(info[1][1]) == 0, (st, info)
+        assert np.array_equal(g.get_basis(1, 1)[0], b)
+        e = g.row_expo(1)
+        pm = [g.lll_ex_plane(1, 0, k) for k in range(4)]
+        pr = [g.lll_ex_plane(1, 1, k) for k in range(4)]
+        for k in range(prec // 53, 4):
+            assert not pm[k].any() and not pr[k].any(), (prec, k)
+        wm = wr = wb = mp.mpf(0)
+        for i in range(d):
+            for j in range(i + 1):
+                got = mp.fsum(mp.mpf(float(p[i, j])) for p in pr) * mp.mpf(2) ** int(e[i] + e[j])
+                wr = max(wr, abs(got - r[i][j]) / r[i][i])
+                wb = max(wb, abs(got - r[i][j]) / (norm[i] * norm[j]))
+                if j < i:
+                    got = mp.fsum(mp.mpf(float(p[i, j])) for p in pm) * mp.mpf(2) ** int(e[i] - e[j])
+                    wm = max(wm, abs(got - mu[i][j]) / max(1, abs(mu[i][j])))
+        worst[prec] = (wm, wr)
+        worst_bb[prec] = wb
+        if prec == 212:
+            for pl, tri in ((pm, np.tril_indices(d, -1)), (pr, np.tril_indices(d))):
+                ent = np.stack([p[tri] for p in pl], axis=1)
+                bad, _ = F.normalisation(ent, 4)
+                assert not bad, bad[:4]
+                nz2, nz3 = np.count_nonzero(ent[:, 2]), np.count_nonzero(ent[:, 3])
+                assert 2 * nz2 > len(ent) and 2 * nz3 > len(ent), (nz2, nz3, len(ent))
+    g.close()
+    lg = lambda x: float(mp.log(x, 2)) if x else float("-inf")  # noqa: E731
+    C.note(lambda: ("%s vs exact Gram-Schmidt: mu 2^%.1f / 2^%.1f / 2^%.1f, r 2^%.1f / 2^%.1f / 2^%.1f at 53 / 106 / 212 bits"
+                    % ((name,) + tuple(lg(worst[p][k]) for k in (0, 1) for p in (53, 106, 212))),
+                    "%s: r relative to |b_i| |b_j| 2^%.1f / 2^%.1f / 2^%.1f"
+                    % ((name,) + tuple(lg(worst_bb[p]) for p in (53, 106, 212)))))
+    for k in (0, 1):
+        assert worst[53][k] <= mp.mpf(2) ** -40
+        assert worst[106][k] <= mp.mpf(2) ** -92
+        assert worst[212][k] <= mp.mpf(2) ** -192
+        assert worst[212][k] * 2 ** 90 < worst[106][k]
 
 
 def _rows_in_qary_lattice(b_in, b_out):
