@@ -17,16 +17,18 @@
 // branch instructions, 0.81 of the vector issue port (profiles/r05_enum_pmc_summary.txt).  The siblings of a node,
 // however, are a function of three wave-uniform numbers (the centre c, the parent's distance, r_kk): child j of the
 // zig-zag has x_j = round(c) + z_j, dist_j = pd + (x_j - c)^2 r, and the sequence of distances is non-decreasing.  This
-// kernel evaluates the 64 first candidates of a node in the 64 LANES — one fma, one subtract, two multiplies, one
-// add, one compare — and reads the number of surviving children off the ballot (s_ff1 of its complement): the
-// failing test is gone and the later siblings need no test at all (STEP: the next index of the stored count).
-// Every dist_j is produced by the reference's operation sequence, and a node is counted when it is visited, so
-// the visit set and the counts are the reference's bit for bit.
+// kernel evaluates the 61 first candidates of a node in the 64 LANES (z = 0 sits in lane 0 of each of the four
+// 16-lane rows) — one add, two multiplies, one add, one compare — and reads the number of surviving children off the
+// ballot (its popcount - 3): the failing test is gone and the later siblings need no test at all (STEP: the next
+// index of the stored count).  Every dist_j is the double the reference's operation sequence produces (x_j - c is
+// formed as (x_0 - c) + z_j: one rounding of the same real number, see EXPAND), and a node is counted when it is
+// visited, so the visit set and the counts are the reference's bit for bit.
 //
-//   EXPAND(k):  node at level k (column S_k, distance nd).  c = S_k[k-1]; x_0 = roundto(c); lanes j: x_j, dist_j;
-//               m = ballot(dist_j <= pruning_{k-1} maxdist); n = ctz(~m).  n = 0: STEP(k).  Else level registers
-//               (lane k-1): c, x_0, pd = nd, st = (i = 0, sign of the first step, n); push S_k; descend into child 0
-//               (++nodes[k-1]; its distance = lane 0 of dist_j through the LDS crossbar).
+//   EXPAND(k):  node at level k (column S_k, distance nd).  c = S_k[k-1]; x_0 = roundto(c), a = x_0 - c; lanes j:
+//               dist_j = nd + (a + z_j)^2 r; m = ballot(dist_j <= pruning_{k-1} maxdist); m = 0: STEP(k).  Else
+//               n = popcount(m) - 3 and level registers (lane k-1): c, x_0, pd = nd, st = (i = 0, n); push S_k; descend
+//               into child 0 (++nodes[k-1]; its distance = dist_j of z = 0: lane 0 of every 16-lane row, handed to
+//               the row by one DPP move, row_bcast0_f64 — nothing recomputed, nothing through the LDS crossbar).
 //   STEP(k):    st_k.i + 1 < st_k.n: x = x_0 + z(i) (z from a 2 KB table through the scalar cache, as a double),
 //               dist = pd + (x - c)^2 r, S_k = S_{k+1} - x mu_k, EXPAND(k).  Else climb: STEP(k + 1).
 //
@@ -35,7 +37,7 @@
 //     one, each may lower the bound for its next sibling, :97-101);
 //   * the chain of first children below a root of distance exactly 0 (is_svp: x only grows there, :80-89 — by
 //     symmetry those children are the odd indices of the zig-zag over the same centre 0: flag `grow`);
-//   * a node with more than 63 surviving children (flag `more`: the 64th onwards are tested one by one).
+//   * a node whose candidates +-30 all survive (61 children or more: they are tested one by one, the slow levels).
 // A bound that shrinks (a candidate was found) re-tests the not-yet-visited siblings of the active levels and
 // shortens their counts (reprune): a sibling is never visited under a bound it fails, to the granularity at which
 // waves learn of a new bound — enum_phase_kernel's contract as well.
@@ -52,7 +54,7 @@
 //      no bit below the level of the current node is set.  STEP is therefore ONE scalar search: the lowest set bit
 //      of P is the level of the next sibling; an empty P ends the task.
 //   B  level l's lane registers (cs, x0s, pds, st) and its pushed column are valid: set by an expansion with n >= 2
-//      and by the slow levels (zero chain, 63+ children), cleared by a chain descent.  P implies B.
+//      and by the slow levels (zero chain, 61+ children), cleared by a chain descent.  P implies B.
 // A chain descent (n = 1) counts the child, takes its distance and column and clears B: no push, no lane-register
 // write.  The coefficient of a level outside B is roundto(centre) and is not stored: the three rare paths that need
 // the coefficients of the path (a level-1 leaf report, the prefix of a donated task) replay the path from the task's
@@ -70,12 +72,12 @@ namespace fphip
 {
 
 // st: the sibling state of one level (lane = level; CHAIN: of one B level)
-//   hot level     bits 0-6: i, the index of the current child in zig-zag order (0..61); bits 8-14: n, the number of
-//                 surviving children (1..62; CHAIN: 2..62); the direction of the first step is not stored: it is
+//   hot level     bits 0-6: i, the index of the current child in zig-zag order (0..59); bits 8-14: n, the number of
+//                 surviving children (1..60; CHAIN: 2..60); the direction of the first step is not stored: it is
 //                 c >= x_0 again
 //   slow level    (st & 0x7fff) == ST_MARK (i = 100 < n = 127: "a sibling is left" for the hot test, which sends
 //                 every i >= 64 to the general path); bits 17-31: iw, the index of the current child.  Levels of the
-//                 zero chain, levels with 63+ surviving children — and, without CHAIN, lane Lt & 63, the task root's:
+//                 zero chain, levels with 61+ surviving children — and, without CHAIN, lane Lt & 63, the task root's:
 //                 the climb that reaches it ends the task
 //   0             (without CHAIN) nothing left at this level
 #define ST_I(s) ((s)&0x7f)
@@ -146,12 +148,11 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
   char *stk_top      = (char *)stk + (((unsigned)ldsRow << 3) + lane8);
   double *gst = gstk + (size_t)(blockIdx.x * nw + wave) * (size_t)(triL - ldsRow + 1) - ldsRow;
   const double *rptab = &g->mu_sq[0][64];
-  // z_j of this lane's candidate of an expansion (first step up).  Lane 63 holds a NaN: its candidate never
-  // passes, so the complement of the ballot always has a bit set and 63 surviving candidates mean "maybe more"
-  double zz = lane == 63 ? __builtin_nan("") : (double)zig_of(lane, false);
+  // z_j of this lane's candidate of an expansion (first step up): 0 in lane 0 of every 16-lane row (lanes 0, 16,
+  // 32, 48), +1, -1, +2, -2, ... +30, -30 over the other 60 lanes — 61 distinct candidates, z = 0 four times, so that
+  // the first child's distance reaches every lane by one row broadcast (row_bcast0_f64)
+  double zz = (lane & 15) == 0 ? 0.0 : (double)zig_of(lane - (lane >> 4), false);
   FPHIP_IN_VGPR(zz);
-  int zero_a = 0;  // the address operand "lane 0" of a bpermute (opaque: a constant index becomes two v_readlane)
-  asm volatile("" : "+v"(zero_a));
 
   unsigned long long mbits =
       rfl_u64(min(bound_init, __hip_atomic_load(&g->bound_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
@@ -481,13 +482,16 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               asm volatile("");
               const bool fix = (a1 < 0.0) == (c1 > 0.0);
               x1             = fix ? x1 - (a1 + a1) : x1;
-              a1             = fix ? -a1 : a1;
+              // -a1 where fix, as a flip of the sign bit in place: a1 is the operand of every lane's candidate now,
+              // and a select of the pair costs the loop two register copies
+              a1 = __hiloint2double(__double2hiint(a1) ^ (fix ? (int)0x80000000 : 0), __double2loint(a1));
             }
-            // candidate of lane j: x_0 + (0, +1, -1, +2, -2, ... +31, -31) — a set symmetric about x_0, so the
-            // survivors are the first n of the reference's zig-zag WHICHEVER way its first step goes (:71 / :114:
-            // the step that picks a child asks again); the distance by the reference's sequence (:28-29 / :91-92)
-            const double xj  = x1 + zz;
-            const double aj  = xj - c1;
+            // candidates: x_0 + (0, +1, -1, +2, -2, ... +30, -30) — a set symmetric about x_0, so the survivors are
+            // the first n of the reference's zig-zag WHICHEVER way its first step goes (:71 / :114: the step that
+            // picks a child asks again); the distance by the reference's sequence (:28-29 / :91-92).  x_j - c without
+            // x_j: a1 = x_0 - c is exact, x_0 + z an exact integer while |x_0| + 31 <= 2^53, so a1 + z is ONE rounding
+            // of the real number x_j - c, as (x_0 + z) - c is: the same double (tests/test_walk_bcast_model.py).
+            const double aj  = a1 + zz;
             rp_wait(q1);
             const double bnd = rp_p(q1) * maxdist_v;  // partdistbounds[kk-1], enumerate.cpp:218-228
             const double ndj = nd + aj * aj * rp_r(q1);
@@ -504,21 +508,25 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               FPHIP_EXIT();
               break;
             }
-            int n = __builtin_popcountll(m);  // (lane 63 never passes)
-            asm("" : "+s"(n));
-            if (n == 63)
-            {  // 63+ children: the general path
+            // z = 0 sits in four lanes.  The four run the same operations on the same operands, and the distance is
+            // non-decreasing in |a_j| (a square, a product by r > 0 and a sum, each rounded monotonically) with |a1|
+            // the smallest: whenever any candidate passes, z = 0 passes in all four of its lanes — m != 0 means
+            // popcount(m) = 3 + the number of surviving children.  All 64 set: +-30 survive, +-31 may as well.
+            int c = __builtin_popcountll(m);
+            asm("" : "+s"(c));
+            if (c == 64)
+            {  // 61+ children: the general path
               ev = EV_SPECIAL;
               FPHIP_EXIT();
               break;
             }
             // ---- descend into child 0 (++nodes[kk-1])
             const unsigned long long me = lane_bit(kc);
-            if (CHAIN && n == 1)
+            if (CHAIN && c == 4)
             {  // a link of a chain: level kc has no sibling to come back to — nothing of it is stored
               B &= ~me;
               cnt32 = add_bit(me, cnt32);
-              nd    = nd + a1 * a1 * rp_r(q1);  // the child's distance (lane 0's ndj: z = 0), in every lane's own registers
+              nd    = row_bcast0_f64(ndj);  // the child's distance: ndj of z = 0, lane 0 of every row
               S     = S - (DUAL ? a1 : x1) * mk1;
               --kc;
               continue;
@@ -533,12 +541,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             cs    = sel_f64(me, c1, cs);
             x0s   = sel_f64(me, x1, x0s);
             pds   = sel_f64(me, nd, pds);
-            st    = wl_i32(n << 8, kc, st);
+            st    = wl_i32((c - 3) << 8, kc, st);
             cnt32 = add_bit(me, cnt32);
-            if constexpr (CHAIN)
-              nd = nd + a1 * a1 * rp_r(q1);  // the first child's distance, as in the chain descent
-            else
-              nd = bp_f64(ndj, zero_a);  // lane 0: the first child's distance
+            nd    = row_bcast0_f64(ndj);  // the first child's distance, as in the chain descent
             S     = S - (DUAL ? a1 : x1) * mk1;
             --kc;
           }
@@ -677,7 +682,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
         }
         else
         {
-          // the expansion by hand of a slow level: the zero chain, 63+ surviving children, or a level the mask holds
+          // the expansion by hand of a slow level: the zero chain, 61+ surviving children, or a level the mask holds
           // for no reason any more.  Only the first child is established here; its siblings are the slow step's.
           const bool nz = __builtin_amdgcn_ballot_w64(nd != 0.0) != 0ull;
           if (zc && nz)

@@ -32,6 +32,20 @@ __device__ __forceinline__ double bp_f64(double v, int addr4)
 {
   return __hiloint2double(bp_i32(__double2hiint(v), addr4), bp_i32(__double2loint(v), addr4));
 }
+// Lane 0 of each 16-lane ROW into every lane of that row: DPP row_newbcast:0 (gfx90a and later), ONE vector move
+// of the 64-bit pair and nothing on the LDS crossbar.  A wave-wide broadcast where lanes 0, 16, 32 and 48 hold
+// the same value — the walk's candidate layout puts z = 0 there.  EXEC must be full (the callers sit in wave-uniform
+// control flow): a DPP read of a disabled lane returns nothing useful.  The s_nop covers the two wait states
+// between a VALU write of `v` and its DPP read: the compiler cannot see the hazard inside the asm statement.
+__device__ __forceinline__ double row_bcast0_f64(double v)
+{
+  double r;
+  asm("s_nop 1\n\t"
+      "v_mov_b64_dpp %0, %1 row_newbcast:0 row_mask:0xf bank_mask:0xf"
+      : "=v"(r)
+      : "v"(v));
+  return r;
+}
 // 4 * level in a VGPR: the address operand of the bpermutes of one level
 __device__ __forceinline__ int lane_addr(int level)
 {
