@@ -43,6 +43,7 @@ class EnumOpts(ctypes.Structure):
         ("gather", GATHER_CB),
         ("gather_user", ctypes.c_void_p),
         ("ordered", ctypes.c_int),
+        ("target", ctypes.c_void_p),  # closest-vector mode: d doubles (NULL: shortest-vector enumeration)
     ]
 
 

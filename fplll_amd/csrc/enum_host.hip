@@ -44,6 +44,22 @@ __global__ void enum_walk_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf o
                                  unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
                                  unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
                                  const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
+// closest-vector mode (fphip_enum_opts::target): the same kernel texts compiled with the zero chain switched off and
+// the zero leaf reported (enum_kernel_cvp.hip, enum_walk_cvp.hip)
+template <bool MU_LDS, bool SUBS, bool DUAL>
+__global__ void enum_phase_cvp_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, int stop,
+                                      unsigned task_lo, unsigned task_hi, const unsigned *idxlist, int launch_idx,
+                                      int count_nodes, unsigned budget, const double *xhi_root, double *gstk, int Tsplit,
+                                      unsigned *qh, const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
+template <bool MU_LDS, bool DUAL, bool CHAIN>
+__global__ void enum_walk_cvp_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, unsigned task_lo,
+                                     unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
+                                     unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
+                                     const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
+template <bool DUAL>
+__global__ void enum_bfs_cvp_kernel(DevShared *g, double maxdist, QueueMem *qm, TaskBuf f0, TaskBuf f1, TaskBuf fin, int L0,
+                                    int nlev, int floor_level, float heavy, int count_nodes, int compact_n, int shard_index,
+                                    int shard_count);
 // enum_deal.hip: the content-sorted snake deal of a multi-rank call on the device
 size_t deal_work_bytes(unsigned n);
 unsigned deal_tasks_device(hipStream_t s, const unsigned long long *keys, const double *pd, const unsigned *slot_of,
@@ -193,7 +209,7 @@ static int fail(fphip_ctx *ctx, const char *fmt, ...)
       return fail(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" int fphip_abi_version(void) { return 2; }
+extern "C" int fphip_abi_version(void) { return 3; }
 
 extern "C" int fphip_device_count(void)
 {
@@ -816,6 +832,25 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
              "ordered enumeration: not with dual, findsubsols, more than 64 rows, several ranks or a bound exchange");
     return FPHIP_UNSUPPORTED;
   }
+  // closest-vector mode, v1: primal, candidates only, one chunk of levels, one rank, the device's own order
+  const bool cvp = o.target != nullptr;
+  if (cvp)
+  {
+    const char *with = dual                                        ? "dual (the reference refuses the pair as well)"
+                       : subs                                      ? "findsubsols"
+                       : ordered                                   ? "ordered (reference-order mode)"
+                       : d > 64                                    ? "more than 64 rows"
+                       : (o.shard_count > 1 || o.exchange || o.gather) ? "several ranks (shard_count, exchange, gather)"
+                                                                   : nullptr;
+    if (with)
+    {
+      snprintf(ctx->err, sizeof ctx->err, "closest-vector enumeration (target): not with %s", with);
+      return FPHIP_UNSUPPORTED;
+    }
+    for (int i = 0; i < d; ++i)
+      if (!std::isfinite(o.target[i]))
+        return fail(ctx, "closest-vector enumeration: target coordinate %d is not finite", i);
+  }
   if (!(maxdist >= 0.0))
     return FPHIP_UNSUPPORTED;
   for (int i = 0; i < d; ++i)
@@ -845,7 +880,7 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
       o.target_tasks > 0 ? o.target_tasks
                          : env_int("FPHIP_TARGET_TASKS", gh_nodes > 1e8 ? 65536 : 32768);
   int overflow_retries = 0;  // split-launch overflows under sharding answered by a smaller task target
-  if (o.min_nodes_decline > 0)
+  if (o.min_nodes_decline > 0 && !cvp)  // (the estimate is one of a tree around the origin: no word on a target's)
   {
     double tot = 0;
     for (int k = 0; k < d; ++k)
@@ -884,6 +919,12 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
     __atomic_store_n(&ctx->ordered_running, 1, __ATOMIC_RELEASE);
     ordered_flag.p = &ctx->ordered_running;
   }
+  // closest-vector mode: the root task's column is the target (center_partsum[i] = target_coord[i],
+  // enumerate.cpp:85-89), rows >= d zero; every centre below comes out of it by the walk's S_k = S_{k+1} - x mu_k
+  double root_col[64];
+  memset(root_col, 0, sizeof root_col);
+  if (cvp)
+    memcpy(root_col, o.target, (size_t)d * sizeof(double));
 restart:
   // ---- upload the block: rdiag, pruning, mu rows (triangular) ---------------------------------
   DevShared *st = ctx->stage;
@@ -942,7 +983,10 @@ restart:
   // root task: level d, zero partial sums, zero prefix, zero partial distance (the breadth-first
   // stage reads its first frontier from buf[1] and leaves the final task list in buf[0])
   int cur = use_bfs ? 1 : 0;
-  HIPCHK(ctx, hipMemsetAsync(ctx->buf[cur].col, 0, 64 * sizeof(double), ctx->stream));
+  if (cvp)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->buf[cur].col, root_col, sizeof root_col, hipMemcpyHostToDevice, ctx->stream));
+  else
+    HIPCHK(ctx, hipMemsetAsync(ctx->buf[cur].col, 0, 64 * sizeof(double), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->buf[cur].x, 0, 64 * sizeof(double), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->buf[cur].pd, 0, sizeof(double), ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ctx->buf[cur].level, &d, sizeof(int), hipMemcpyHostToDevice,
@@ -1159,7 +1203,10 @@ restart:
       const int cnt     = (bfs_sharded || filter) ? 1 : cnt_bfs;
       if (filter)
         bfs_sharded = true;
-      if (dual)
+      if (cvp)
+        hipLaunchKernelGGL((enum_bfs_cvp_kernel<false>), dim3(grid), dim3(threads), 0, ctx->stream, ctx->g, maxdist,
+                           ctx->qm, fa, fb, ctx->buf[0], Lv, nlev, Lend, heavy, cnt, compact_n, o.shard_index, scount);
+      else if (dual)
         hipLaunchKernelGGL((enum_bfs_kernel<true>), dim3(grid), dim3(threads), 0, ctx->stream, ctx->g, maxdist,
                            ctx->qm, fa, fb, ctx->buf[0], Lv, nlev, Lend, heavy, cnt, compact_n, o.shard_index, scount);
       else
@@ -1485,8 +1532,9 @@ restart:
         // (ordered: no donation either — a window is complete when its launch returns)
         const unsigned bud =
             (in_final && round < max_rounds && (!subs || env_int("FPHIP_SUBS_DONATE", 1) != 0) && !ordered) ? budget : 0u;
-#define FPHIP_LAUNCH(M, S, D)                                                                       \
-  hipLaunchKernelGGL((enum_phase_kernel<M, S, D>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
+#define FPHIP_LAUNCH(M, S, D) FPHIP_LAUNCH_K(enum_phase_kernel, M, S, D)
+#define FPHIP_LAUNCH_K(KERNEL, M, S, D)                                                             \
+  hipLaunchKernelGGL((KERNEL<M, S, D>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
                      ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, stop, lo, hi, idxl, launch_idx,     \
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],          \
                      (regioned && !shard_now && !order_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
@@ -1494,8 +1542,9 @@ restart:
         // the walk launches (no sub-solutions): the third-generation walk — single-child descents store nothing,
         // the next sibling is one scalar search (enum_walk_kernel<.., CHAIN = true>, enum_walk.hip); FPHIP_WALK3=0
         // keeps the second generation (<.., false>), FPHIP_WALK2=0 enum_phase_kernel (the A/B partners)
-#define FPHIP_LAUNCH2_K(M, D, C)                                                                     \
-  hipLaunchKernelGGL((enum_walk_kernel<M, D, C>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
+#define FPHIP_LAUNCH2_K(M, D, C) FPHIP_LAUNCH2_KK(enum_walk_kernel, M, D, C)
+#define FPHIP_LAUNCH2_KK(KERNEL, M, D, C)                                                            \
+  hipLaunchKernelGGL((KERNEL<M, D, C>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
                      ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,           \
                      count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],  \
                      (regioned && !shard_now && !order_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
@@ -1508,7 +1557,28 @@ restart:
     else                                                                                             \
       FPHIP_LAUNCH2_K(M, D, false);                                                                  \
   } while (0)
-        if (in_final && !subs && walk2)
+        if (cvp)
+        {  // closest-vector mode: the same choice among the kernels compiled for it (primal, no sub-solutions)
+          if (in_final && walk2 && walk3)
+          {
+            if (mu_lds)
+              FPHIP_LAUNCH2_KK(enum_walk_cvp_kernel, true, false, true);
+            else
+              FPHIP_LAUNCH2_KK(enum_walk_cvp_kernel, false, false, true);
+          }
+          else if (in_final && walk2)
+          {
+            if (mu_lds)
+              FPHIP_LAUNCH2_KK(enum_walk_cvp_kernel, true, false, false);
+            else
+              FPHIP_LAUNCH2_KK(enum_walk_cvp_kernel, false, false, false);
+          }
+          else if (mu_lds)
+            FPHIP_LAUNCH_K(enum_phase_cvp_kernel, true, false, false);
+          else
+            FPHIP_LAUNCH_K(enum_phase_cvp_kernel, false, false, false);
+        }
+        else if (in_final && !subs && walk2)
         {
           if (dual && mu_lds)
             FPHIP_LAUNCH2(true, true);
@@ -1532,8 +1602,10 @@ restart:
         else
           FPHIP_LAUNCH(false, true, false);
 #undef FPHIP_LAUNCH
+#undef FPHIP_LAUNCH_K
 #undef FPHIP_LAUNCH2
 #undef FPHIP_LAUNCH2_K
+#undef FPHIP_LAUNCH2_KK
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         ++launch_idx;
@@ -1682,7 +1754,30 @@ restart:
   uint64_t total = 0;
   for (int k = 0; k <= d; ++k)
     nodes_out[k] = (k < d) ? st->nodes[k] : 0;
-  if (o.shard_index == 0)
+  if (cvp)
+  {
+    // enumerate_base.cpp:180-183 with a target: one node off every level k0 < i < d, k0 the level at which
+    // prepare_enumeration's rounding descent stopped (enumerate.cpp:167-215, restated in double with its operation
+    // sequence: newcenter -= x[j] * mut[k][j], j ascending; roundto: ties away from zero; the loop tests maxdist, not
+    // the pruned bounds).  The reference subtracts in unsigned arithmetic without a check: a level the walk never
+    // reached ends at 2^64 - 1 there, and here.
+    double xr[64];
+    double newdist = 0.0;
+    int k          = d - 1;
+    for (; k >= 0 && newdist <= maxdist; --k)
+    {
+      double newcenter = o.target[k];
+      for (int j = k + 1; j < d; ++j)
+        newcenter -= xr[j] * mut[(size_t)k * d + j];
+      xr[k]              = std::round(newcenter);
+      const double alpha = xr[k] - newcenter;
+      newdist += alpha * alpha * rdiag[k];
+    }
+    const int k0 = k + 1;
+    for (int i = k0 + 1; i < d; ++i)
+      nodes_out[i]--;
+  }
+  else if (o.shard_index == 0)
     for (int k = 1; k < d; ++k)
       nodes_out[k]--;  // enumerate_base.cpp:181-184: the initial descent is not counted
   for (int k = 0; k < d; ++k)

@@ -53,6 +53,13 @@
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off  (no FMA contraction: fplll's
 // arithmetic is separate multiply and add, nr/nr_FP_d.inl:178, baseline x86-64 build).
+//
+// Closest-vector mode (FPHIP_CVP): enum_kernel_cvp.hip compiles the text of enum_phase_kernel
+// and enum_bfs_kernel a second time with FPHIP_CVP = 1, into kernels of another name (enum_phase_cvp_kernel,
+// enum_bfs_cvp_kernel): the reference's walk with a target (!is_svp) takes the zig-zag at every node, the root
+// included (enumerate_base.cpp:80), and hands a leaf at distance exactly 0 to the evaluator (:44 / :99) — the
+// `if constexpr (CVP)` lines below; the target itself sits in the root task's column.  Without the macro the text is
+// what it was: the kernels of the shortest-vector walk keep their names and their code.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,6 +67,17 @@
 #include "enum_device.h"
 #include "enum_wave.h"
 
+
+#ifndef FPHIP_CVP
+#define FPHIP_CVP 0
+#endif
+#if FPHIP_CVP
+#define FPHIP_PHASE_KERNEL enum_phase_cvp_kernel
+#define FPHIP_BFS_KERNEL enum_bfs_cvp_kernel
+#else
+#define FPHIP_PHASE_KERNEL enum_phase_kernel
+#define FPHIP_BFS_KERNEL enum_bfs_kernel
+#endif
 
 namespace fphip
 {
@@ -90,13 +108,14 @@ namespace fphip
 // (8 waves per SIMD = at most 64 VGPRs: the walk is issue-bound and loses a tenth of its rate at 7)
 template <bool MU_LDS, bool SUBS, bool DUAL>
 __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
-    enum_phase_kernel(DevShared *__restrict__ g, HostCtl *__restrict__ h, TaskBuf in, TaskBuf out,
+    FPHIP_PHASE_KERNEL(DevShared *__restrict__ g, HostCtl *__restrict__ h, TaskBuf in, TaskBuf out,
                       int d, int Lmax, int stop, unsigned task_lo, unsigned task_hi,
                       const unsigned *__restrict__ idxlist, int launch_idx, int count_nodes,
                       unsigned budget, const double *__restrict__ xhi_root, double *__restrict__ gstk,
                       int Tsplit, unsigned *__restrict__ qh, const unsigned *__restrict__ rcnt, unsigned rcap,
                       unsigned long long bound_init)
 {
+  constexpr bool CVP = FPHIP_CVP != 0;  // closest-vector mode: see the header
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -553,7 +572,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           // the test and the selection of the step are scalar-unit work.
           int pdor = pdlo | pdhi;
           asm volatile("" : "+s"(pdor));  // (one 32-bit OR, not a 64-bit compare of a register pair)
-          const bool zig = pdor != 0;
+          bool zig       = pdor != 0;
+          if constexpr (CVP)
+            zig = true;  // (!is_svp: the zig-zag whatever the distance above)
           int stepi      = zig ? dxk : 1;
           asm volatile("" : "+s"(stepi));  // (keeps the select in front of the int -> double conversion)
           xk += (double)stepi;
@@ -629,7 +650,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           FPHIP_DESCEND(FPHIP_PUSH(k < Ts, k, tri8(k + 1)), k = kc);
           if (k != 0)
             continue;  // → CHILD chain at the new level
-          ev = (__builtin_amdgcn_ballot_w64(nd > 0.0) != 0ull) ? EV_REPORT : EV_RESTEP;
+          ev = (CVP || __builtin_amdgcn_ballot_w64(nd > 0.0) != 0ull) ? EV_REPORT : EV_RESTEP;  // (:44: || !is_svp)
         }
       }
       if (ev == EV_EMIT)
@@ -665,7 +686,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       }
       else if (ev == EV_LEAF)
       {  // level 0, :97-101: report (nd > 0), then the next sibling of level 0
-        if (__builtin_amdgcn_ballot_w64(nd > 0.0) != 0ull)
+        if (CVP || __builtin_amdgcn_ballot_w64(nd > 0.0) != 0ull)  // (:99: || !is_svp)
         {
           report(nd);
           FPHIP_JOIN();
@@ -712,17 +733,19 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
 }
 
 #define FPHIP_INST(M, S, D)                                                                            \
-  template __global__ void enum_phase_kernel<M, S, D>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int,  \
+  template __global__ void FPHIP_PHASE_KERNEL<M, S, D>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int,  \
                                                       int, int, unsigned, unsigned, const unsigned *,  \
                                                       int, int, unsigned, const double *, double *, int, \
                                                       unsigned *, const unsigned *, unsigned,            \
                                                       unsigned long long);
 FPHIP_INST(true, false, false)
 FPHIP_INST(false, false, false)
+#if !FPHIP_CVP  // (a target comes without sub-solutions and without dual)
 FPHIP_INST(true, true, false)
 FPHIP_INST(false, true, false)
 FPHIP_INST(true, false, true)
 FPHIP_INST(false, false, true)
+#endif
 #undef FPHIP_INST
 
 // ---------------------------------------------------------------------------------------------
@@ -758,7 +781,7 @@ __device__ __forceinline__ float wave_sum_f32(float v)
 
 template <bool DUAL>
 __global__ void __launch_bounds__(1024)
-    enum_bfs_kernel(DevShared *__restrict__ g, double maxdist, QueueMem *__restrict__ qm,
+    FPHIP_BFS_KERNEL(DevShared *__restrict__ g, double maxdist, QueueMem *__restrict__ qm,
                     TaskBuf f0, TaskBuf f1, TaskBuf fin, int L0, int nlev, int floor_level, float heavy,
                     int count_nodes, int compact_n, int shard_index, int shard_count)
 {
@@ -837,7 +860,7 @@ __global__ void __launch_bounds__(1024)
           nd                = mine ? nd : __builtin_inf();
         }
         int dx    = (c >= x) ? 1 : -1;  // :71 (ddx == sign(dx) throughout)
-        const bool zig = pdu != 0.0;    // :80-89: partdist exactly 0 above: x only grows (is_svp)
+        const bool zig = FPHIP_CVP != 0 || pdu != 0.0;  // :80-89: partdist exactly 0 above: x only grows (is_svp)
         while (nd <= bnd)               // :31 / :93 (NaN fails)
         {
           ++cnt;  // ++nodes[kc]
@@ -894,10 +917,13 @@ __global__ void __launch_bounds__(1024)
     }
   }
 }
-template __global__ void enum_bfs_kernel<false>(DevShared *, double, QueueMem *, TaskBuf, TaskBuf, TaskBuf, int, int,
-                                                int, float, int, int, int, int);
+template __global__ void FPHIP_BFS_KERNEL<false>(DevShared *, double, QueueMem *, TaskBuf, TaskBuf, TaskBuf, int, int,
+                                                 int, float, int, int, int, int);
+#if !FPHIP_CVP
 template __global__ void enum_bfs_kernel<true>(DevShared *, double, QueueMem *, TaskBuf, TaskBuf, TaskBuf, int, int,
                                                int, float, int, int, int, int);
+
+// (the top walk and the task helpers below are compiled once: blocks above 64 rows take no target)
 
 // ---------------------------------------------------------------------------------------------
 // Blocks larger than 64 (up to 256): the levels 64..d-1.  The TOP of the tree is walked with two
@@ -1303,5 +1329,6 @@ __global__ void __launch_bounds__(256)
       keys[tp] = ((unsigned long long)h1 << 32) | h2;
   }
 }
+#endif  // !FPHIP_CVP
 
 }  // namespace fphip

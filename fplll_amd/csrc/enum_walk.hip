@@ -60,6 +60,13 @@
 // the coefficients of the path (a level-1 leaf report, the prefix of a donated task) replay the path from the task's
 // root column with the walk's own operation sequence, so the bits are identical; reprune touches B levels only.
 //
+// Closest-vector mode (FPHIP_CVP): enum_walk_cvp.hip compiles this text a second time with
+// FPHIP_CVP = 1, into kernels of another name (enum_walk_cvp_kernel).  The reference's walk with a target
+// (!is_svp, enumerate_base.cpp:44 / :80 / :99) differs in what the `if constexpr (CVP)` lines say and in nothing else:
+// no zero chain (the zig-zag at every node, the root included), and a leaf at distance exactly 0 is a candidate.  The
+// target itself sits in the root task's column.  Without the macro the text is what it was: the kernels of the
+// shortest-vector walk keep their names and their code.
+//
 // Build: like enum_kernel.hip (-ffp-contract=off; -structurizecfg-skip-uniform-regions, no lifetime markers).
 
 #include <hip/hip_runtime.h>
@@ -67,6 +74,15 @@
 
 #include "enum_device.h"
 #include "enum_wave.h"
+
+#ifndef FPHIP_CVP
+#define FPHIP_CVP 0
+#endif
+#if FPHIP_CVP
+#define FPHIP_WALK_KERNEL enum_walk_cvp_kernel
+#else
+#define FPHIP_WALK_KERNEL enum_walk_kernel
+#endif
 
 namespace fphip
 {
@@ -106,13 +122,14 @@ __device__ __forceinline__ double rp_r2(const v2u &q) { return __hiloint2double(
 
 template <bool MU_LDS, bool DUAL, bool CHAIN>
 __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
-    enum_walk_kernel(DevShared *__restrict__ g, HostCtl *__restrict__ h, TaskBuf in, TaskBuf out,
+    FPHIP_WALK_KERNEL(DevShared *__restrict__ g, HostCtl *__restrict__ h, TaskBuf in, TaskBuf out,
                      int d, int Lmax, unsigned task_lo, unsigned task_hi,
                      const unsigned *__restrict__ idxlist, int launch_idx, int count_nodes,
                      unsigned budget, const double *__restrict__ xhi_root, double *__restrict__ gstk,
                      int Tsplit, unsigned *__restrict__ qh, const unsigned *__restrict__ rcnt, unsigned rcap,
                      unsigned long long bound_init)
 {
+  constexpr bool CVP = FPHIP_CVP != 0;  // closest-vector mode: see the header
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (wave-uniform: the per-wave bases in SGPRs)
@@ -274,6 +291,8 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
     // the chain of first children below a root of distance exactly 0 goes through the general path (slow
     // levels) until the first step away from it: every level is "special" while zc holds
     bool zc = __builtin_amdgcn_ballot_w64(pd0 != 0.0) == 0ull;
+    if constexpr (CVP)
+      zc = false;  // (!is_svp, :80: no zero chain — the root expands as a zig-zag like every other node)
     // CHAIN: the sibling masks (see the header): the task root's level holds no sibling, an empty P ends the task
     unsigned long long P = 0ull, B = 0ull;
     // else: the climb that reaches the root's level ends the task: a slow marker in its lane (lane 0 when Lt = 64 —
@@ -648,7 +667,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             al = -al;
           }
           int dx         = (c0 >= x) ? 1 : -1;
-          const bool zig = __builtin_amdgcn_ballot_w64(nd != 0.0) != 0ull;
+          bool zig       = __builtin_amdgcn_ballot_w64(nd != 0.0) != 0ull;
+          if constexpr (CVP)
+            zig = true;
           const double r0 = g->rdiag[0], p0 = g->pruning[0];
           for (;;)
           {
@@ -656,7 +677,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             if (__builtin_amdgcn_ballot_w64(ndc <= p0 * maxdist) == 0ull)
               break;
             cnt += (lane == 0) ? 1ull : 0ull;
-            if (__builtin_amdgcn_ballot_w64(ndc > 0.0) != 0ull)
+            if (CVP || __builtin_amdgcn_ballot_w64(ndc > 0.0) != 0ull)  // (:44 / :99: newdist > 0.0 || !is_svp)
             {
               if constexpr (!CHAIN)
               {  // (the leaf's coefficient reaches the record through lane 0 of the level registers)
@@ -737,7 +758,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
         const int cur   = ST_IW(stk_);
         const double x0 = rl_f64(x0s, k), ck = rl_f64(cs, k), pk = rl_f64(pds, k);
         const double rk = g->rdiag[k], pr = g->pruning[k];
-        const bool grow = __builtin_amdgcn_ballot_w64(pk != 0.0) == 0ull;
+        bool grow       = __builtin_amdgcn_ballot_w64(pk != 0.0) == 0ull;
+        if constexpr (CVP)
+          grow = false;
         const bool down = __builtin_amdgcn_ballot_w64(ck >= x0) == 0ull;
         const int nxt   = grow ? (cur == 0 ? 1 : cur + 2) : cur + 1;
         xk              = x0 + (double)zig_of(nxt, down);
@@ -838,18 +861,22 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
 }
 
 #define FPHIP_INST(M, D, C)                                                                             \
-  template __global__ void enum_walk_kernel<M, D, C>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int, \
+  template __global__ void FPHIP_WALK_KERNEL<M, D, C>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int, \
                                                   unsigned, unsigned, const unsigned *, int, int,       \
                                                   unsigned, const double *, double *, int, unsigned *,   \
                                                   const unsigned *, unsigned, unsigned long long);
 FPHIP_INST(true, false, false)
 FPHIP_INST(false, false, false)
+#if !FPHIP_CVP  // (no dual instantiation with a target: the reference refuses the pair, enumerate.cpp:73)
 FPHIP_INST(true, true, false)
 FPHIP_INST(false, true, false)
+#endif
 FPHIP_INST(true, false, true)
 FPHIP_INST(false, false, true)
+#if !FPHIP_CVP
 FPHIP_INST(true, true, true)
 FPHIP_INST(false, true, true)
+#endif
 #undef FPHIP_INST
 
 }  // namespace fphip

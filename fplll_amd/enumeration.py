@@ -92,8 +92,8 @@ def mut_from_mu(mu):
 def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0, shard_count=1,
                     exchange=None, exchange_chunks=1, target_tasks=0, phase_growth=0,
                     waves_per_block=0, min_nodes_decline=0, dual=False, findsubsols=False,
-                    log=None, gather=None, ordered=False):
-    """Run one SVP enumeration on the GPU through the C ABI.
+                    log=None, gather=None, ordered=False, target=None):
+    """Run one enumeration on the GPU through the C ABI.
 
     mut[i*d+j] = mu(j,i) for j>i; rdiag, pruning (or None), maxdist normalised like the reference
     hands them to a plugin.  ``evaluator.eval_sol(coords, dist, max_dist) -> new max_dist`` is
@@ -102,7 +102,10 @@ def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0,
     [bytes of rank 0, bytes of rank 1, ...]`` the all-gather the work movement between ranks rides on
     (fphip_gather_cb: distributed.make_gather).  ``ordered=True``: reference-order mode — the evaluator sees exactly
     the reference's candidates in the reference's order (fphip_enum_opts::ordered); ``res.nodes`` is then the
-    device's work, per level >= the reference's counts.
+    device's work, per level >= the reference's counts.  ``target`` (d float64s, the coordinates
+    EnumerationDyn::enumerate receives as target_coord): closest-vector mode (fphip_enum_opts::target) — every x
+    around the target within the bounds is a candidate, distance 0 included; not together with dual, findsubsols,
+    ordered, more than 64 rows or several ranks (``Unsupported``).
     """
     lib = ctx.lib
     mut = np.ascontiguousarray(mut, dtype=np.float64)
@@ -174,6 +177,11 @@ def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0,
     opts.min_nodes_decline = min_nodes_decline
     opts.gather = _lib.GATHER_CB(_gc) if gather is not None else _lib.GATHER_CB()
     opts.ordered = int(bool(ordered))
+    if target is not None:
+        target = np.ascontiguousarray(target, dtype=np.float64)  # (a local: alive until the call has returned)
+        if target.shape != (d,):
+            raise ValueError("target: expected %d coordinates, got shape %r" % (d, target.shape))
+        opts.target = target.ctypes.data
     nodes = np.zeros(d + 1, dtype=np.uint64)
     stats = _lib.EnumStats()
     rc = lib.fphip_enum_run(ctx.handle, d, ctypes.c_double(maxdist),
@@ -188,3 +196,15 @@ def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0,
     if rc != _lib.FPHIP_OK:
         raise _lib.HipError("fphip_enum_run failed: %s" % ctx.last_error())
     return EnumResult(nodes, stats, state["maxdist"])
+
+
+def closest_vector_block(ctx, mut, rdiag, target, maxdist, pruning=None):
+    """The closest lattice vector to ``target`` within squared distance ``maxdist`` (normalised like rdiag): one
+    closest-vector enumeration under a BEST_N(1) evaluator, the radius shrinking with every candidate.  Returns
+    ``(dist, x)`` — x the coefficients of the vector, a tuple of d floats — or ``None`` when nothing lies within the
+    radius (the pruned bounds, where given)."""
+    ev = FastEvaluator(1, EVALSTRATEGY_BEST_N_SOLUTIONS)
+    enumerate_block(ctx, mut, rdiag, pruning, maxdist, ev, target=target)
+    if ev.empty():
+        return None
+    return ev.solutions[0]

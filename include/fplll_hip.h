@@ -132,6 +132,10 @@ typedef struct fphip_enum_opts
    * shard_count > 1 or an `exchange` callback (its bound is a foreign one).  FPHIP_ORDER_WINDOWS="first[,growth]" sets the window schedule (default "1024,8"; "0": one
    * window). */
   int ordered;
+  /* non-NULL → closest-vector mode: dim doubles, the target's coordinates as EnumerationDyn::enumerate receives
+   * them (target_coord[first .. last), enumerate.cpp:85-89); NULL: shortest-vector enumeration.  See fphip_enum_run.
+   * (The last field, added with ABI version 3: a caller that zero-initialises the struct keeps what it had.) */
+  const double *target;
 } fphip_enum_opts;
 
 typedef struct fphip_enum_stats
@@ -160,6 +164,23 @@ typedef struct fphip_enum_stats
  *                       (enum/enumerate_base.cpp:31-33 incl. the :181-184 compensation)
  * Level bound = pruning[k]*maxdist; a node survives iff newdist <= bound (NaN-safe form).
  * With opts->ordered, nodes_out is the device's work (a superset of the reference's walk): per level >= fplll's counts.
+ *
+ * Closest-vector mode (opts->target non-NULL): the call EnumerationDyn::enumerate(first, last, maxdist, 0,
+ * target_coord, {}, pruning) makes with a non-empty target (what closest_vector runs, svpcvp.cpp).  The centres
+ * start from the target instead of 0 (center_partsum[i] = target[i]); a candidate x with squared distance `dist`
+ * stands for the lattice point sum x_i b_i, dist = sum_i (x_i - c_i)^2 r_ii with c_i = target[i] - sum_{j>i} x_j mu(j,i)
+ * — the squared distance of that point to the target sum target[i] b*_i, normalised like rdiag.  Every x whose
+ * partial distances pass the level bounds is visited — there is no half tree, x and -x are different candidates —
+ * and a leaf at distance exactly 0.0 (a target that lies in the lattice) is reported like any other.
+ * nodes_out follows the reference's rule for such a call: the plain number of nodes visited per level, minus 1
+ * (mod 2^64, as the reference's unchecked unsigned decrement, enumerate_base.cpp:180-183) on every level i with
+ * k0 < i < dim, where k0 is the level at which prepare_enumeration's rounding descent from the target stopped
+ * (enumerate.cpp:167-215; 0 when the descent stays within maxdist — it tests maxdist, not the pruned bounds).
+ * opts->min_nodes_decline is ignored (the Gaussian-heuristic estimate is one of a shortest-vector tree): a
+ * closest-vector call is never declined for being small.  fphip_enum_lower_bound and the callback's bound protocol
+ * are unchanged.  v1 limits, each declined with FPHIP_UNSUPPORTED and a fphip_last_error text before anything is
+ * launched: target together with dual (the reference refuses that too, enumerate.cpp:73), with findsubsols, with
+ * ordered, with dim > 64, with shard_count > 1, exchange or gather.  A non-finite target coordinate is FPHIP_ERROR.
  */
 int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const double *mut, const double *rdiag,
                    const double *pruning, const fphip_enum_opts *opts, fphip_sol_cb cb,
