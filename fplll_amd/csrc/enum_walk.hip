@@ -29,6 +29,13 @@
 //               n = popcount(m) - 3 and level registers (lane k-1): c, x_0, pd = nd, st = (i = 0, n); push S_k; descend
 //               into child 0 (++nodes[k-1]; its distance = dist_j of z = 0: lane 0 of every 16-lane row, handed to
 //               the row by one DPP move, row_bcast0_f64 — nothing recomputed, nothing through the LDS crossbar).
+//               The vector test runs around rint(c), NOT roundto(c): on a tie (a = +-0.5 exactly) the two nearest
+//               integers see the same multiset of |a + z_j| over the 61 candidates, hence the same popcount and the
+//               same distance of z = 0 — and z = +-1 shares that distance, so a tie has no child or at least two
+//               and is never a chain link.  roundto()'s tie test therefore sits on the descent WITH siblings alone, in
+//               a block of its own behind the fail, special, popcount-64 and chain exits, where x_0 is corrected (and
+//               a's sign flipped: the dual column update multiplies by it) before they are stored and used.  The
+//               special exits redo the expansion by hand with their own roundto (tests/test_walk_tie_model.py).
 //   STEP(k):    st_k.i + 1 < st_k.n: x = x_0 + z(i) (z from a 2 KB table through the scalar cache, as a double),
 //               dist = pd + (x - c)^2 r, S_k = S_{k+1} - x mu_k, EXPAND(k).  Else climb: STEP(k + 1).
 //
@@ -494,17 +501,14 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               mk1 = ld_row(mu_b, (unsigned)kc * MUROW8, lane8);
             ka -= 4;
             c1 = bp_f64(S, ka);  // center[kk-1]
+            // x_0 = rint(c) here, not roundto(c): on a tie (a1 = +-0.5 exactly) the two nearest integers give the same
+            // multiset of |a1 + z_j| over the 61 candidates — {0.5, 0.5, 1.5, 1.5, ... 29.5, 29.5, 30.5} — so the
+            // ballot's popcount and the distance of z = 0 are those of roundto's x_0 (tests/test_walk_tie_model.py),
+            // and z = +-1 shares z = 0's distance: a tie has 0 or >= 2 children, never a chain link.  The tie is
+            // corrected where x_0 is stored: in the descent with siblings below.  (The special exits redo the
+            // expansion by hand with their own roundto.)
             x1 = rint(c1);
             a1 = x1 - c1;
-            if (__builtin_amdgcn_ballot_w64(fabs(a1) == 0.5) != 0ull)
-            {  // roundto(): ties away from zero
-              asm volatile("");
-              const bool fix = (a1 < 0.0) == (c1 > 0.0);
-              x1             = fix ? x1 - (a1 + a1) : x1;
-              // -a1 where fix, as a flip of the sign bit in place: a1 is the operand of every lane's candidate now,
-              // and a select of the pair costs the loop two register copies
-              a1 = __hiloint2double(__double2hiint(a1) ^ (fix ? (int)0x80000000 : 0), __double2loint(a1));
-            }
             // candidates: x_0 + (0, +1, -1, +2, -2, ... +30, -30) — a set symmetric about x_0, so the survivors are
             // the first n of the reference's zig-zag WHICHEVER way its first step goes (:71 / :114: the step that
             // picks a child asks again); the distance by the reference's sequence (:28-29 / :91-92).  x_j - c without
@@ -549,6 +553,14 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               S     = S - (DUAL ? a1 : x1) * mk1;
               --kc;
               continue;
+            }
+            if (__builtin_amdgcn_ballot_w64(fabs(a1) == 0.5) != 0ull)
+            {  // roundto(): ties away from zero
+              asm volatile("");
+              const bool fix = (a1 < 0.0) == (c1 > 0.0);
+              x1             = fix ? x1 - (a1 + a1) : x1;
+              // -a1 where fix (the operand of the dual column update), as a flip of the sign bit in place
+              a1 = __hiloint2double(__double2hiint(a1) ^ (fix ? (int)0x80000000 : 0), __double2loint(a1));
             }
             // (CHAIN: siblings follow) S_k is needed again when x[kc] steps to a sibling
             FPHIP_PUSH(kc < Ts - 1, kc + 1, tri8(kc + 2));
