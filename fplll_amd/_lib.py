@@ -14,6 +14,7 @@ FPHIP_OK = 0
 FPHIP_UNSUPPORTED = 1
 FPHIP_ERROR = -1
 ENUM_MAX_DIM = 256
+FPHIP_BKZ_TRANSFORM = 0x4000  # fphip_gso_bkz / fphip_gso_bkz_strategies: keep the tracked u in step with b
 
 SOL_CB = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_void_p, ctypes.c_double,
                           ctypes.POINTER(ctypes.c_double))

@@ -30,6 +30,13 @@
 //     this wave, depth-first — the reference's visiting order, so the in-kernel evaluator
 //     (best solution so far, radius shrinks to its norm) ends on the reference's vector;
 //   * post-processing works on lanes = columns; row swaps of the gcd tree are slot swaps.
+//
+// The transformation matrix (FPHIP_BKZ_U, see lll_wave.h): bkz_kernel_u.hip compiles this text a second time
+// with FPHIP_BKZ_U = 1 into bkz_kernel_u — MatGSO(b, u, ...) under bkz_reduction(b, u, param), bkz.cpp:849-927.
+// Every row operation on b is then applied to the same slot of u (P.u, [d][ldd], lane c owns column c): the AXPYs
+// of LLL / size reduction in babai_impl, the insertions below; move_row and the gcd tree's swaps act on the slot
+// table, which u shares.  u leaves in position order through P.u2.  ustats[5] counts the insertions by kind
+// (fphip_gso_bkz_insert_stats).  The numpy replay in tests/test_bkz_transform_cpu.py is the model.
 
 #include "lll_wave.h"
 
@@ -62,10 +69,17 @@ __device__ __forceinline__ void refloat_and_invalidate(Lattice<NQ> &T, LllCtx &C
 
 // info[4] per lattice: tours, enumeration nodes (low / high 32 bits), enumeration calls
 // status: 1 RED_SUCCESS, 8 RED_BKZ_LOOPS_LIMIT, <= 0 the failing LLL status (lll_wave.h)
+#if FPHIP_BKZ_U
+#define FPHIP_BKZ_KERNEL bkz_kernel_u
+#define FPHIP_BKZ_U_PARAM , unsigned long long *ustats
+#else
+#define FPHIP_BKZ_KERNEL bkz_kernel
+#define FPHIP_BKZ_U_PARAM
+#endif
 template <int NQ>
 __global__ void __launch_bounds__(256)
-    bkz_kernel(GsoBatch P, int block_size, double delta, double eta, double logdelta,
-               int use_max_loops, int max_loops, int stack_doubles)
+    FPHIP_BKZ_KERNEL(GsoBatch P, int block_size, double delta, double eta, double logdelta,
+                     int use_max_loops, int max_loops, int stack_doubles FPHIP_BKZ_U_PARAM)
 {
   constexpr int IPS = (NQ + 1) / 2;
   extern __shared__ __attribute__((aligned(16))) char bkz_smem[];
@@ -101,6 +115,10 @@ __global__ void __launch_bounds__(256)
     T.narrow_flag = (int *)T.rexp;
     T.np          = 0;
     T.f32ok       = all_rows_narrow<NQ>(P, (size_t)L, lane);
+#if FPHIP_BKZ_U
+    T.u = P.u + (size_t)L * d * ldd;
+    unsigned ucnt_rot = 0, ucnt_unit = 0, ucnt_gen = 0;  // insertions of this lattice by kind
+#endif
     LllCtx C{P.gf + (size_t)L * d * ldd, P.vc + (size_t)L * d};
     double *mu_blk = P.enum_mu + (size_t)L * (64 * 63 / 2);  // scaled mu rows of the current block
     SlotMap<NQ> M;
@@ -110,6 +128,9 @@ __global__ void __launch_bounds__(256)
       for (int q = 0; q < NQ; ++q)
         M.sl[q] = lane + 64 * q;
       lll_write_ordered<NQ>(T, M, P.b2 + (size_t)L * d * ldn);
+#if FPHIP_BKZ_U
+      u_write_ordered<NQ>(T, M, P.u2 + (size_t)L * d * ldd);
+#endif
       continue;
     }
     lll_init_state<NQ>(T, C, M);
@@ -374,6 +395,9 @@ __global__ void __launch_bounds__(256)
             const int iv       = onm ? 63 - __clzll((long long)onm) : -1;
             if (nz == 1)
             {
+#if FPHIP_BKZ_U
+              ++ucnt_rot;
+#endif
               if (iv > 0)
               {
                 rotate_right<NQ>(M, kappa, kappa + iv, lane);
@@ -393,6 +417,16 @@ __global__ void __launch_bounds__(256)
                 const int c = lane + 64 * q;
                 bv[q]       = (c < n) ? T.b[(size_t)st * ldn + c] : 0;
               }
+#if FPHIP_BKZ_U
+              ++ucnt_unit;
+              long long uv[NQ];  // u[kappa+iv] += sum_i (sol_iv * sol_i) u[kappa+i]
+#pragma unroll
+              for (int q = 0; q < NQ; ++q)
+              {
+                const int c = lane + 64 * q;
+                uv[q]       = (c < d) ? T.u[(size_t)st * ldd + c] : 0;
+              }
+#endif
               for (int i = 0; i < bs; ++i)
               {
                 const double xi = g_rl_f64(best_x, i);
@@ -408,7 +442,26 @@ __global__ void __launch_bounds__(256)
                     bv[q] = (long long)((unsigned long long)bv[q] +
                                         (unsigned long long)T.b[(size_t)si * ldn + c] * (unsigned long long)lx);
                 }
+#if FPHIP_BKZ_U
+#pragma unroll
+                for (int q = 0; q < NQ; ++q)
+                {
+                  const int c = lane + 64 * q;
+                  if (c < d)
+                    uv[q] = (long long)((unsigned long long)uv[q] +
+                                        (unsigned long long)T.u[(size_t)si * ldd + c] * (unsigned long long)lx);
+                }
+#endif
               }
+#if FPHIP_BKZ_U
+#pragma unroll
+              for (int q = 0; q < NQ; ++q)
+              {
+                const int c = lane + 64 * q;
+                if (c < d)
+                  T.u[(size_t)st * ldd + c] = uv[q];
+              }
+#endif
               store_row_and_refloat<NQ>(T, st, bv);
               after_rowop<NQ>(T, C, M, kappa + iv);
               vp = min(vp, kappa);
@@ -435,9 +488,15 @@ __global__ void __launch_bounds__(256)
                     if (c < n)
                       T.b[(size_t)si * ldn + c] = -T.b[(size_t)si * ldn + c];
                   }
+#if FPHIP_BKZ_U
+                  u_row_negate<NQ>(T, si);
+#endif
                 }
               }
               x = fabs(x);
+#if FPHIP_BKZ_U
+              ++ucnt_gen;
+#endif
               __threadfence_block();
               auto swap_rows = [&](int pa, int pb)
               {  // row_swap: the rows are re-floated below, so swapping their slots is equivalent
@@ -482,6 +541,9 @@ __global__ void __launch_bounds__(256)
                                           (unsigned long long)T.b[(size_t)ssrc * ldn + c] *
                                               (unsigned long long)lq);
                       }
+#if FPHIP_BKZ_U
+                      u_row_addmul<NQ>(T, sdst, ssrc, lq);  // row_addmul(k - off, k, q) on u
+#endif
                       __threadfence_block();
                     }
                     const double t = xk;
@@ -509,6 +571,18 @@ __global__ void __launch_bounds__(256)
         break;
     }
     lll_write_ordered<NQ>(T, M, P.b2 + (size_t)L * d * ldn);
+#if FPHIP_BKZ_U
+    u_write_ordered<NQ>(T, M, P.u2 + (size_t)L * d * ldd);
+    if (lane == 0)
+    {
+      if (ucnt_rot)
+        atomicAdd(&ustats[0], (unsigned long long)ucnt_rot);
+      if (ucnt_unit)
+        atomicAdd(&ustats[1], (unsigned long long)ucnt_unit);
+      if (ucnt_gen)
+        atomicAdd(&ustats[2], (unsigned long long)ucnt_gen);
+    }
+#endif
     if (lane == 0)
     {
       P.status[L]           = status;
@@ -522,9 +596,16 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+#if FPHIP_BKZ_U
+template __global__ void bkz_kernel_u<1>(GsoBatch, int, double, double, double, int, int, int, unsigned long long *);
+template __global__ void bkz_kernel_u<2>(GsoBatch, int, double, double, double, int, int, int, unsigned long long *);
+template __global__ void bkz_kernel_u<3>(GsoBatch, int, double, double, double, int, int, int, unsigned long long *);
+template __global__ void bkz_kernel_u<4>(GsoBatch, int, double, double, double, int, int, int, unsigned long long *);
+#else
 template __global__ void bkz_kernel<1>(GsoBatch, int, double, double, double, int, int, int);
 template __global__ void bkz_kernel<2>(GsoBatch, int, double, double, double, int, int, int);
 template __global__ void bkz_kernel<3>(GsoBatch, int, double, double, double, int, int, int);
 template __global__ void bkz_kernel<4>(GsoBatch, int, double, double, double, int, int, int);
+#endif
 
 }  // namespace fphip

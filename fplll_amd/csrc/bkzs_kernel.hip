@@ -37,6 +37,12 @@
 // in LDS (device recursion would need scratch memory, which the DMA ring's vmcnt accounting
 // excludes): block sizes strictly decrease, the host rejects strategies that nest deeper than
 // FPHIP_BKZS_MAX_DEPTH.
+//
+// The transformation matrix (FPHIP_BKZ_U, see lll_wave.h and bkz_kernel.hip): bkzs_kernel_u.hip compiles this
+// text a second time with FPHIP_BKZ_U = 1 into bkzs_kernel_u / bkzd_kernel_u.  Every place that changes a row of
+// b then acts on the same slot of u: babai_impl's AXPYs, the primal insertions, the dual insertions (note the
+// dual tree's direction: u[k] -= q u[k - off] where b's rows are combined), the row additions and subtractions
+// of rerandomize_block.  ustats[5]: insertions by kind (fphip_gso_bkz_insert_stats).
 
 #include "lll_wave.h"
 
@@ -154,10 +160,21 @@ __device__ __forceinline__ void refloat_and_invalidate2(Lattice<NQ> &T, LllCtx &
 // bkz.cpp:148-193,240-248; the prelude lll() :576-577 and the closing hkz() :627-641 selected by
 // run_mode: 1 prelude, 2 tours, 4 closing hkz).  Everything it adds sits behind `if constexpr
 // (DUALS)`: the DUALS = false instantiation is the kernel of §4f, instruction for instruction.
+#if FPHIP_BKZ_U
+#define FPHIP_BKZS_KERNEL bkzs_kernel_u
+#define FPHIP_BKZD_KERNEL bkzd_kernel_u
+#define FPHIP_BKZ_U_PARAM , unsigned long long *ustats
+#define FPHIP_BKZ_U_ARG , ustats
+#else
+#define FPHIP_BKZS_KERNEL bkzs_kernel
+#define FPHIP_BKZD_KERNEL bkzd_kernel
+#define FPHIP_BKZ_U_PARAM
+#define FPHIP_BKZ_U_ARG
+#endif
 template <int NQ, bool DUALS>
 __device__ __forceinline__ void
 bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size, int top_flags,
-          double delta, double eta, double logdelta, int max_loops, int stack_doubles, int run_mode)
+          double delta, double eta, double logdelta, int max_loops, int stack_doubles, int run_mode FPHIP_BKZ_U_PARAM)
 {
   constexpr int IPS = (NQ + 1) / 2;
   using RingT       = ReduceRing<NQ>;
@@ -195,6 +212,10 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
     T.narrow_flag = (int *)T.rexp;
     T.np          = 0;
     T.f32ok       = all_rows_narrow<NQ>(P, (size_t)L, lane);
+#if FPHIP_BKZ_U
+    T.u = P.u + (size_t)L * d * ldd;
+    unsigned ucnt_rot = 0, ucnt_unit = 0, ucnt_gen = 0, ucnt_dual = 0, ucnt_rr = 0;  // this lattice's, by kind
+#endif
     LllCtx C{P.gf + (size_t)L * d * ldd, P.vc + (size_t)L * d};
     // scaled mu rows of the block being enumerated: in LDS behind this wave's column stack when the
     // host asked for it (top_flags bit 30: few lattices per CU, where the L1 latency of every row
@@ -219,6 +240,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
       for (int q = 0; q < NQ; ++q)
         M.sl[q] = lane + 64 * q;
       lll_write_ordered<NQ>(T, M, P.b2 + (size_t)L * d * ldn);
+#if FPHIP_BKZ_U
+      u_write_ordered<NQ>(T, M, P.u2 + (size_t)L * d * ldd);
+#endif
       continue;
     }
     lll_init_state<NQ>(T, C, M);
@@ -657,6 +681,10 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                   T.b[(size_t)sa * ldn + c]   = (long long)(ad ? va + vb : va - vb);
                 }
               }
+#if FPHIP_BKZ_U
+              u_row_addmul<NQ>(T, sa, sb, ad ? 1ll : -1ll);  // row_add(a, b) / row_sub(a, b) on u
+              ++ucnt_rr;
+#endif
               __threadfence_block();
             }
             refloat_and_invalidate2<NQ>(T, C, M, lo, hi);  // row_op_end(min_row, max_row)
@@ -1045,6 +1073,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
           {
             handled  = true;
             F.rerand = 0;
+#if FPHIP_BKZ_U
+            ++ucnt_dual;
+#endif
             // the evaluator's vector is index-reversed first (enumerate.cpp:154-158)
             double sx = __shfl(best_x, in ? bs - 1 - lane : 0);
             sx        = in ? sx : 0.0;
@@ -1085,6 +1116,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                         (long long)((unsigned long long)T.b[(size_t)si * ldn + c] +
                                     (unsigned long long)biv[q] * (unsigned long long)lx);
                 }
+#if FPHIP_BKZ_U
+                u_row_addmul<NQ>(T, si, siv, lx);  // u[kappa+i] += (-sol_iv * sol_i) u[kappa+iv]
+#endif
               }
               __threadfence_block();
               refloat_and_invalidate2<NQ>(T, C, M, kappa, kappa + bs);  // row_op_end(kappa, kappa + bs)
@@ -1108,6 +1142,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                     if (c < n)
                       T.b[(size_t)si * ldn + c] = -T.b[(size_t)si * ldn + c];
                   }
+#if FPHIP_BKZ_U
+                  u_row_negate<NQ>(T, si);
+#endif
                 }
               }
               x = fabs(x);
@@ -1154,6 +1191,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                               (long long)((unsigned long long)T.b[(size_t)sdst * ldn + c] -
                                           (unsigned long long)T.b[(size_t)ssrc * ldn + c] * (unsigned long long)lq);
                       }
+#if FPHIP_BKZ_U
+                      u_row_addmul<NQ>(T, sdst, ssrc, -lq);  // the dual tree: u[k] -= q u[k - off]
+#endif
                       __threadfence_block();
                     }
                     const double t = xk;
@@ -1183,6 +1223,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
           const int iv       = onm ? 63 - __clzll((long long)onm) : -1;
           if (nz == 1)
           {
+#if FPHIP_BKZ_U
+            ++ucnt_rot;
+#endif
             if (iv > 0)
             {
               rotate_right<NQ>(M, kappa, kappa + iv, lane);
@@ -1201,6 +1244,16 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
               const int c = lane + 64 * q;
               bv[q]       = (c < n) ? T.b[(size_t)st * ldn + c] : 0;
             }
+#if FPHIP_BKZ_U
+            ++ucnt_unit;
+            long long uv[NQ];  // u[kappa+iv] += sum_i (sol_iv * sol_i) u[kappa+i]
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+            {
+              const int c = lane + 64 * q;
+              uv[q]       = (c < d) ? T.u[(size_t)st * ldd + c] : 0;
+            }
+#endif
             for (int i = 0; i < bs; ++i)
             {
               const double xi = g_rl_f64(best_x, i);
@@ -1216,7 +1269,26 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                   bv[q] = (long long)((unsigned long long)bv[q] +
                                       (unsigned long long)T.b[(size_t)si * ldn + c] * (unsigned long long)lx);
               }
+#if FPHIP_BKZ_U
+#pragma unroll
+              for (int q = 0; q < NQ; ++q)
+              {
+                const int c = lane + 64 * q;
+                if (c < d)
+                  uv[q] = (long long)((unsigned long long)uv[q] +
+                                      (unsigned long long)T.u[(size_t)si * ldd + c] * (unsigned long long)lx);
+              }
+#endif
             }
+#if FPHIP_BKZ_U
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+            {
+              const int c = lane + 64 * q;
+              if (c < d)
+                T.u[(size_t)st * ldd + c] = uv[q];
+            }
+#endif
             store_row_and_refloat<NQ>(T, st, bv);
             after_rowop<NQ>(T, C, M, kappa + iv);
             vp = min(vp, kappa);
@@ -1229,6 +1301,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
           }
           else
           {
+#if FPHIP_BKZ_U
+            ++ucnt_gen;
+#endif
             double x = in ? best_x : 0.0;
             for (int i = 0; i < bs; ++i)
             {
@@ -1242,6 +1317,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                   if (c < n)
                     T.b[(size_t)si * ldn + c] = -T.b[(size_t)si * ldn + c];
                 }
+#if FPHIP_BKZ_U
+                u_row_negate<NQ>(T, si);
+#endif
               }
             }
             x = fabs(x);
@@ -1287,6 +1365,9 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
                             (long long)((unsigned long long)T.b[(size_t)sdst * ldn + c] +
                                         (unsigned long long)T.b[(size_t)ssrc * ldn + c] * (unsigned long long)lq);
                     }
+#if FPHIP_BKZ_U
+                    u_row_addmul<NQ>(T, sdst, ssrc, lq);  // row_addmul(k - off, k, q) on u
+#endif
                     __threadfence_block();
                   }
                   const double t = xk;
@@ -1345,6 +1426,22 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
         status = status_before;  // the closing passes keep RED_SUCCESS / RED_BKZ_LOOPS_LIMIT
     }
     lll_write_ordered<NQ>(T, M, P.b2 + (size_t)L * d * ldn);
+#if FPHIP_BKZ_U
+    u_write_ordered<NQ>(T, M, P.u2 + (size_t)L * d * ldd);
+    if (lane == 0)
+    {
+      if (ucnt_rot)
+        atomicAdd(&ustats[0], (unsigned long long)ucnt_rot);
+      if (ucnt_unit)
+        atomicAdd(&ustats[1], (unsigned long long)ucnt_unit);
+      if (ucnt_gen)
+        atomicAdd(&ustats[2], (unsigned long long)ucnt_gen);
+      if (ucnt_dual)
+        atomicAdd(&ustats[3], (unsigned long long)ucnt_dual);
+      if (ucnt_rr)
+        atomicAdd(&ustats[4], (unsigned long long)ucnt_rr);
+    }
+#endif
     if (lane == 0)
     {
       P.status[L]           = status;
@@ -1365,17 +1462,25 @@ bkzs_body(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_s
 // the same schedule with the dual blocks of self-dual BKZ (the host selects it for BKZ_SD_VARIANT)
 template <int NQ>
 __global__ void __launch_bounds__(256)
-    bkzd_kernel(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size, int top_flags,
-                double delta, double eta, double logdelta, int max_loops, int stack_doubles, int run_mode)
+    FPHIP_BKZD_KERNEL(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size, int top_flags,
+                      double delta, double eta, double logdelta, int max_loops, int stack_doubles,
+                      int run_mode FPHIP_BKZ_U_PARAM)
 {
   bkzs_body<NQ, true>(P, S, mailbox, abort_flag, block_size, top_flags, delta, eta, logdelta, max_loops,
-                      stack_doubles, run_mode);
+                      stack_doubles, run_mode FPHIP_BKZ_U_ARG);
 }
 
+#if FPHIP_BKZ_U
+template __global__ void bkzd_kernel_u<1>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int, unsigned long long *);
+template __global__ void bkzd_kernel_u<2>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int, unsigned long long *);
+template __global__ void bkzd_kernel_u<3>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int, unsigned long long *);
+template __global__ void bkzd_kernel_u<4>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int, unsigned long long *);
+#else
 template __global__ void bkzd_kernel<1>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int);
 template __global__ void bkzd_kernel<2>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int);
 template __global__ void bkzd_kernel<3>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int);
 template __global__ void bkzd_kernel<4>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, int);
+#endif
 
 }  // namespace sdv
 
@@ -1383,16 +1488,23 @@ template __global__ void bkzd_kernel<4>(GsoBatch, BkzStrat, BkzMail *, int *, in
 // schedule without the dual blocks
 template <int NQ>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NQ <= 1 ? 2 : 1, 8)))
-    bkzs_kernel(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size, int top_flags,
-                double delta, double eta, double logdelta, int max_loops, int stack_doubles)
+    FPHIP_BKZS_KERNEL(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size, int top_flags,
+                      double delta, double eta, double logdelta, int max_loops, int stack_doubles FPHIP_BKZ_U_PARAM)
 {
   sdv::bkzs_body<NQ, false>(P, S, mailbox, abort_flag, block_size, top_flags, delta, eta, logdelta,
-                            max_loops, stack_doubles, 7);
+                            max_loops, stack_doubles, 7 FPHIP_BKZ_U_ARG);
 }
 
+#if FPHIP_BKZ_U
+template __global__ void bkzs_kernel_u<1>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, unsigned long long *);
+template __global__ void bkzs_kernel_u<2>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, unsigned long long *);
+template __global__ void bkzs_kernel_u<3>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, unsigned long long *);
+template __global__ void bkzs_kernel_u<4>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int, unsigned long long *);
+#else
 template __global__ void bkzs_kernel<1>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int);
 template __global__ void bkzs_kernel<2>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int);
 template __global__ void bkzs_kernel<3>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int);
 template __global__ void bkzs_kernel<4>(GsoBatch, BkzStrat, BkzMail *, int *, int, int, double, double, double, int, int);
+#endif
 
 }  // namespace fphip

@@ -209,7 +209,7 @@ static int fail(fphip_ctx *ctx, const char *fmt, ...)
       return fail(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" int fphip_abi_version(void) { return 3; }
+extern "C" int fphip_abi_version(void) { return 4; }
 
 extern "C" int fphip_device_count(void)
 {

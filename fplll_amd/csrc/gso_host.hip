@@ -57,6 +57,21 @@ __global__ void bkzd_kernel(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort
                             int top_flags, double delta, double eta, double logdelta, int max_loops,
                             int stack_doubles, int run_mode);
 }
+// the same three with the transformation matrix u (FPHIP_BKZ_TRANSFORM): bkz_kernel_u.hip, bkzs_kernel_u.hip
+template <int NQ>
+__global__ void bkz_kernel_u(GsoBatch P, int block_size, double delta, double eta, double logdelta,
+                             int use_max_loops, int max_loops, int stack_doubles, unsigned long long *ustats);
+template <int NQ>
+__global__ void bkzs_kernel_u(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size,
+                              int top_flags, double delta, double eta, double logdelta, int max_loops,
+                              int stack_doubles, unsigned long long *ustats);
+namespace sdv
+{
+template <int NQ>
+__global__ void bkzd_kernel_u(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size,
+                              int top_flags, double delta, double eta, double logdelta, int max_loops,
+                              int stack_doubles, int run_mode, unsigned long long *ustats);
+}
 template <int NQ> __global__ void hlll_kernel(HhBatch P, double delta, double theta, long long iter_cap);
 template <int NQ> __global__ void hh_blocked_kernel(HhBatch P, double *Tbuf);
 struct HlllX
@@ -141,6 +156,11 @@ struct fphip_gso
   long long *sess_in_d = nullptr;  // device: positions then rows of the caller's row operations
   long long *sess_in_h = nullptr;  // pinned staging of the same
   char *sess_out_h     = nullptr;  // pinned: the state in position order after the last session call
+  // FPHIP_BKZ_TRANSFORM: the BKZ call in progress carries u (the _u kernels run, u / u2 are swapped with b / b2);
+  // the insertion counters of that call on the device (allocated by the first such call) and as read back
+  bool bkz_u                       = false;
+  unsigned long long *bkz_stats_d  = nullptr;
+  unsigned long long bkz_stats[5]  = {0, 0, 0, 0, 0};
 };
 
 static int gfail(fphip_ctx *ctx, const char *what, hipError_t e)
@@ -312,6 +332,8 @@ extern "C" void fphip_gso_destroy(fphip_gso *g)
     fphip_dev_free(g->P.u, fphip_ctx_stream(g->ctx));
   if (g->P.u2)
     fphip_dev_free(g->P.u2, fphip_ctx_stream(g->ctx));
+  if (g->bkz_stats_d)
+    fphip_dev_free(g->bkz_stats_d, fphip_ctx_stream(g->ctx));
   if (g->P.lll_info)
     fphip_dev_free(g->P.lll_info, fphip_ctx_stream(g->ctx));
   if (g->P.enum_mu)
@@ -379,6 +401,48 @@ static int transform_guard(fphip_gso *g, const char *what)
   snprintf(fphip_ctx_errbuf(g->ctx), 512, "%s: the transformation matrix u is tracked (fphip_gso_enable_transform) and "
            "this entry point does not update it; fphip_gso_lll / fphip_gso_lll_flags do", what);
   return FPHIP_UNSUPPORTED;
+}
+
+// FPHIP_BKZ_TRANSFORM of the two BKZ entry points.  begin: the flag needs a tracked u; the insertion counters
+// (fphip_gso_bkz_insert_stats) start at zero on the device — the array exists only once the flag has been used.
+// end: the counters of the call's launches come back, and the object forgets the mode.
+static int bkz_transform_begin(fphip_gso *g, bool want, const char *what)
+{
+  g->bkz_u = false;
+  memset(g->bkz_stats, 0, sizeof g->bkz_stats);
+  if (!want)
+    return FPHIP_OK;
+  if (!g->P.u)
+  {
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "%s: FPHIP_BKZ_TRANSFORM needs a transformation matrix on the device: "
+             "call fphip_gso_enable_transform first", what);
+    return FPHIP_ERROR;
+  }
+  if (!g->bkz_stats_d)
+    GCHK(fphip_dev_alloc((void **)&g->bkz_stats_d, sizeof g->bkz_stats, fphip_ctx_stream(g->ctx)));
+  GCHK(hipMemsetAsync(g->bkz_stats_d, 0, sizeof g->bkz_stats, fphip_ctx_stream(g->ctx)));
+  g->bkz_u = true;
+  return FPHIP_OK;
+}
+static void bkz_transform_end(fphip_gso *g)
+{
+  if (g->bkz_u && g->bkz_stats_d)
+    if (hipMemcpy(g->bkz_stats, g->bkz_stats_d, sizeof g->bkz_stats, hipMemcpyDeviceToHost) != hipSuccess)
+      memset(g->bkz_stats, 0, sizeof g->bkz_stats);
+  g->bkz_u = false;
+}
+struct BkzTransformScope
+{
+  fphip_gso *g;
+  ~BkzTransformScope() { bkz_transform_end(g); }
+};
+
+extern "C" int fphip_gso_bkz_insert_stats(const fphip_gso *g, unsigned long long counts[5])
+{
+  if (!g || !counts)
+    return FPHIP_ERROR;
+  memcpy(counts, g->bkz_stats, sizeof g->bkz_stats);
+  return FPHIP_OK;
 }
 
 static int launch(fphip_gso *g, int kmin, int kend, double eta, int mode, const LllArgs *la = nullptr)
@@ -1249,8 +1313,9 @@ static int bkz_launch(fphip_gso *g, int block_size, double delta, double eta, in
 {
   if (int rcg = session_guard(g, "bkz"))
     return rcg;
-  if (int rct = transform_guard(g, "bkz"))
-    return rct;
+  if (!g->bkz_u)
+    if (int rct = transform_guard(g, "bkz"))
+      return rct;
   const int need = (g->P.d > g->P.n ? g->P.d : g->P.n);
   const int nq   = (need + 63) / 64;
   const int wpb  = g->waves_per_block;
@@ -1272,7 +1337,17 @@ static int bkz_launch(fphip_gso *g, int block_size, double delta, double eta, in
     grid = cap;
   hipStream_t s     = fphip_ctx_stream(g->ctx);
   const double logd = std::log(delta);
-  if (lds > 64 * 1024)
+  if (lds > 64 * 1024 && g->bkz_u)
+  {
+    switch (nq)
+    {
+    case 1: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    case 2: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    case 3: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    default: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    }
+  }
+  else if (lds > 64 * 1024)
   {
     switch (nq)
     {
@@ -1283,6 +1358,15 @@ static int bkz_launch(fphip_gso *g, int block_size, double delta, double eta, in
     }
   }
   GCHK(hipEventRecord(g->ev[0], s));
+  if (g->bkz_u)
+    switch (nq)
+    {
+    case 1: hipLaunchKernelGGL(bkz_kernel_u<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
+    case 2: hipLaunchKernelGGL(bkz_kernel_u<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
+    case 3: hipLaunchKernelGGL(bkz_kernel_u<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
+    default: hipLaunchKernelGGL(bkz_kernel_u<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
+    }
+  else
   switch (nq)
   {
   case 1: hipLaunchKernelGGL(bkz_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles); break;
@@ -1298,6 +1382,8 @@ static int bkz_launch(fphip_gso *g, int block_size, double delta, double eta, in
   GCHK(hipMemcpy(st_out, g->P.status, sizeof(int) * g->P.batch, hipMemcpyDeviceToHost));
   GCHK(hipMemcpy(info_out, g->P.lll_info, sizeof(int) * 4 * g->P.batch, hipMemcpyDeviceToHost));
   std::swap(g->P.b, g->P.b2);  // the kernel wrote the rows in position order into b2
+  if (g->bkz_u)
+    std::swap(g->P.u, g->P.u2);  // ... and those of u into u2 (every launch, whatever its statuses)
   // identity-layout GSO of the current bases (same values: every entry is a function of b)
   int rc = launch(g, 0, g->P.d, 0.0, 2);
   if (rc == FPHIP_OK)
@@ -1549,9 +1635,15 @@ extern "C" int fphip_gso_bkz(fphip_gso *g, int block_size, double delta, double 
   FPHIP_RANGE("fphip_gso_bkz");
   if (!g)
     return FPHIP_ERROR;
-  if (block_size > 64 || (flags & ~(0x4 | 0x8 | 0x20 | 0x40)))
+  if (block_size > 64 || (flags & ~(0x4 | 0x8 | 0x20 | 0x40 | 0x4000)))
     return FPHIP_UNSUPPORTED;  // blocks beyond one wavefront / other BKZ variants: fplll's CPU code
-  int rc = ensure_lll_buffers(g);
+  // FPHIP_BKZ_TRANSFORM (0x4000): bkz_kernel_u keeps u in step with b (without it a tracked u is refused, bkz_launch)
+  int rc = bkz_transform_begin(g, (flags & 0x4000) != 0, "bkz");
+  if (rc != FPHIP_OK)
+    return rc;
+  BkzTransformScope u_scope{g};
+  flags &= ~0x4000;
+  rc = ensure_lll_buffers(g);
   if (rc != FPHIP_OK)
     return rc;
   const size_t B = (size_t)g->P.batch, d = g->P.d;
@@ -2210,7 +2302,7 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
   if (g)
     if (int rcg = session_guard(g, "bkz_strategies"))
       return rcg;
-  if (g)
+  if (g && !(flags & 0x4000))
     if (int rct = transform_guard(g, "bkz_strategies"))
       return rct;
   FPHIP_RANGE("fphip_gso_bkz_strategies");
@@ -2221,9 +2313,14 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
   // BKZ_SD_VARIANT (0x100): self-dual BKZ, bkzs_body<NQ, true>
   const bool sd  = (flags & 0x100) != 0;
   const bool sld = (flags & 0x200) != 0;  // BKZ_SLD_RED: slide reduction (slide_tour, bkz.cpp:465-520)
-  if (block_size > 64 || (flags & ~(0x4 | 0x8 | 0x10 | 0x20 | 0x40 | 0x80 | 0x100 | 0x200 | 0x1000 | 0x2000)) ||
-      (sd && sld))
+  if (block_size > 64 ||
+      (flags & ~(0x4 | 0x8 | 0x10 | 0x20 | 0x40 | 0x80 | 0x100 | 0x200 | 0x1000 | 0x2000 | 0x4000)) || (sd && sld))
     return FPHIP_UNSUPPORTED;
+  // FPHIP_BKZ_TRANSFORM (0x4000): bkzs_kernel_u / bkzd_kernel_u keep u in step with b
+  if (int rcu = bkz_transform_begin(g, (flags & 0x4000) != 0, "bkz_strategies"))
+    return rcu;
+  BkzTransformScope u_scope{g};
+  flags &= ~0x4000;
   // BKZ_MAX_TIME (0x8) / BKZ_DUMP_GSO (0x40): one tour per launch, the clock and the dump on the host in between
   TourHooks hooks;
   hooks.use_time = (flags & 0x8) != 0;
@@ -2417,6 +2514,24 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
     grid = cap;
   hipStream_t s     = fphip_ctx_stream(g->ctx);
   const double logd = std::log(delta);
+  if (lds > 64 * 1024 && g->bkz_u)
+  {
+    switch (nq)
+    {
+    case 1: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    case 2: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    case 3: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    default: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+    }
+    if (sd || sld)
+      switch (nq)
+      {
+      case 1: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+      case 2: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+      case 3: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+      default: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
+      }
+  }
   if (lds > 64 * 1024)
   {
     switch (nq)
@@ -2551,7 +2666,29 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
       return rc1;
     GCHK(hipMemsetAsync(d_abort, 0, sizeof(int), s));  // one launch's timeout must not poison the next
     GCHK(hipEventRecord(g->ev[0], s));
-    if (sd || sld)
+    if (g->bkz_u && (sd || sld))
+    {
+      unsigned long long *us = g->bkz_stats_d;
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL(sdv::bkzd_kernel_u<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
+      case 2: hipLaunchKernelGGL(sdv::bkzd_kernel_u<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
+      case 3: hipLaunchKernelGGL(sdv::bkzd_kernel_u<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
+      default: hipLaunchKernelGGL(sdv::bkzd_kernel_u<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
+      }
+    }
+    else if (g->bkz_u)
+    {
+      unsigned long long *us = g->bkz_stats_d;
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL(bkzs_kernel_u<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
+      case 2: hipLaunchKernelGGL(bkzs_kernel_u<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
+      case 3: hipLaunchKernelGGL(bkzs_kernel_u<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
+      default: hipLaunchKernelGGL(bkzs_kernel_u<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
+      }
+    }
+    else if (sd || sld)
     {
       switch (nq)
       {
@@ -2694,6 +2831,8 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
     GCHK(hipMemcpy(st_out, g->P.status, sizeof(int) * B, hipMemcpyDeviceToHost));
     GCHK(hipMemcpy(info_out, g->P.lll_info, sizeof(int) * 4 * B, hipMemcpyDeviceToHost));
     std::swap(g->P.b, g->P.b2);  // the kernel wrote the rows in position order into b2
+    if (g->bkz_u)
+      std::swap(g->P.u, g->P.u2);  // ... and those of u into u2 (every launch, whatever its statuses)
     rc1 = launch(g, 0, g->P.d, 0.0, 2);
     if (rc1 == FPHIP_OK)
       rc1 = launch(g, 0, g->P.d, 0.0, 0);

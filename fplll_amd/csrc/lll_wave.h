@@ -16,6 +16,12 @@ namespace fphip
 #define FPHIP_LLL_STREAM 1
 #endif
 // a Gram row with at most this many unknown entries is completed entry by entry (update_row_cached)
+// The BKZ kernels with the transformation matrix u (bkz_kernel_u.hip, bkzs_kernel_u.hip: the texts of bkz_kernel.hip
+// and bkzs_kernel.hip compiled a second time with FPHIP_BKZ_U = 1, into kernels of another name).  Everything the
+// tracking adds sits behind this switch, so that the plain kernels are the output of the same text as before.
+#ifndef FPHIP_BKZ_U
+#define FPHIP_BKZ_U 0
+#endif
 #ifndef FPHIP_LLL_GRAM_SINGLES
 #define FPHIP_LLL_GRAM_SINGLES 4
 #endif
@@ -1182,7 +1188,11 @@ template <int NQ, class RingT> __device__ __forceinline__ void uniformize(LllFra
   f.T.ldn         = uni(f.T.ldn);
   f.T.row_expo_on = uni(f.T.row_expo_on);
   f.T.b           = uni_ptr(f.T.b);
+#if FPHIP_BKZ_U
+  f.T.u           = uni_ptr(f.T.u);  // bkz_kernel_u.hip / bkzs_kernel_u.hip: babai_impl mirrors every AXPY onto u
+#else
   f.T.u           = nullptr;  // (the BKZ kernels do not track the transformation matrix)
+#endif
   f.T.bfT         = uni_ptr(f.T.bfT);
   f.T.mu          = uni_ptr(f.T.mu);
   f.T.muT         = uni_ptr(f.T.muT);
@@ -1326,6 +1336,53 @@ __device__ __forceinline__ void lll_write_ordered(const Lattice<NQ> &T, const Sl
       const int c = lane + 64 * q;
       if (c < ldn)
         bo[(size_t)p * ldn + c] = T.b[(size_t)s * ldn + c];
+    }
+  }
+}
+
+// ---- the rows of u in the BKZ kernels (FPHIP_BKZ_U): MatGSO's row operations act on u wherever they act on b
+// (gso.cpp:84-158).  u is [d][ldd] in the slots of b's rows, lane c owns column c < d; the same wrap-around
+// arithmetic as b's.  A row of u is never re-floated and invalidates nothing.
+// u[sdst] += x u[ssrc]  (row_addmul; x = -1 / -q: row_sub and the dual tree's direction)
+template <int NQ>
+__device__ __forceinline__ void u_row_addmul(const Lattice<NQ> &T, int sdst, int ssrc, long long x)
+{
+  const int lane = T.lane, d = T.d, ldd = T.ldd;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+  {
+    const int c = lane + 64 * q;
+    if (c < d)
+      T.u[(size_t)sdst * ldd + c] = (long long)((unsigned long long)T.u[(size_t)sdst * ldd + c] +
+                                                (unsigned long long)T.u[(size_t)ssrc * ldd + c] * (unsigned long long)x);
+  }
+}
+// negate_row_of_b(i), gso.cpp:160-176: u's row with it
+template <int NQ> __device__ __forceinline__ void u_row_negate(const Lattice<NQ> &T, int s)
+{
+  const int lane = T.lane, d = T.d, ldd = T.ldd;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+  {
+    const int c = lane + 64 * q;
+    if (c < d)
+      T.u[(size_t)s * ldd + c] = (long long)(0ull - (unsigned long long)T.u[(size_t)s * ldd + c]);
+  }
+}
+// the rows of u in position order (u2), as lll_kernel.hip writes them; swapped with u by the host like b2 / b
+template <int NQ>
+__device__ __forceinline__ void u_write_ordered(const Lattice<NQ> &T, const SlotMap<NQ> &M, long long *uo)
+{
+  const int lane = T.lane, d = T.d, ldd = T.ldd;
+  for (int p = 0; p < d; ++p)
+  {
+    const int s = M.phys(p);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+    {
+      const int c = lane + 64 * q;
+      if (c < ldd)
+        uo[(size_t)p * ldd + c] = T.u[(size_t)s * ldd + c];
     }
   }
 }

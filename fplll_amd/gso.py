@@ -135,7 +135,8 @@ class MatGSOBatch:
     def enable_transform(self, u=None):
         """MatGSO(b, u, ...) with a non-empty u (enable_transform): track the transformation matrix on the device —
         u [batch][d][d] int64, or None for the identity.  lll() then applies every row operation to u as well
-        (gso.cpp:84-158); the entry points that do not raise Unsupported while it is tracked."""
+        (gso.cpp:84-158), and so do bkz() / bkz_strategies() with transform=True; the entry points that do not
+        raise Unsupported while it is tracked."""
         fn = self.lib.fphip_gso_enable_transform
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -296,14 +297,17 @@ class MatGSOBatch:
         return (0x8 if max_time is not None else 0) | (0x40 if dump_gso is not None else 0)
 
     def bkz(self, block_size, delta=LLL_DEF_DELTA, eta=LLL_DEF_ETA, max_loops=0, auto_abort=False, max_time=None,
-            dump_gso=None):
+            dump_gso=None, transform=False):
         """BKZReduction::bkz() with empty strategies on every (LLL-reduced) lattice
         (bkz.cpp:522-668).  max_time (seconds) / dump_gso (file name): BKZ_MAX_TIME / BKZ_DUMP_GSO.
+        transform: FPHIP_BKZ_TRANSFORM — the u of enable_transform() follows every row operation of the run
+        (get_transform() afterwards); without it a tracked u makes the call raise.
         Returns (status[batch], info[batch][4] = tours, nodes lo, nodes hi,
         enumeration calls)."""
         st = np.zeros(self.batch, dtype=np.int32)
         info = np.zeros((self.batch, 4), dtype=np.int32)
         flags = (0x4 if max_loops > 0 else 0) | (0x20 if auto_abort else 0)  # fplll's BKZFlags
+        flags |= _lib.FPHIP_BKZ_TRANSFORM if transform else 0
         flags |= self._bkz_limits(max_time, dump_gso)
         rc = self.lib.fphip_gso_bkz(self.h, block_size, delta, eta, flags,
                                     max_loops, st.ctypes.data_as(ctypes.c_void_p),
@@ -315,7 +319,8 @@ class MatGSOBatch:
 
     def bkz_strategies(self, block_size, strategies, rnd, delta=LLL_DEF_DELTA, eta=LLL_DEF_ETA,
                        max_loops=0, gh_bnd=False, bounded_lll=False, gh_factor=1.1, auto_abort=False,
-                       sd=False, handoff=False, slide=False, prune_in_loop=None, max_time=None, dump_gso=None):
+                       sd=False, handoff=False, slide=False, prune_in_loop=None, max_time=None, dump_gso=None,
+                       transform=False):
         """BKZReduction::bkz() with a strategies table (preprocessing tours, pruning, GH bound,
         rerandomisation; bkz.cpp:43-124, 274-441, 522-668) on every (LLL-reduced) lattice.
         strategies: dict with the flattened arrays of include/fplll_hip.h's fphip_strategies
@@ -331,6 +336,7 @@ class MatGSOBatch:
         on_device): the primal blocks of the top-level tour of at least min_block rows are pruned one by
         one by prune() on their own r-profile (on the device's volume kernel with on_device, default)
         where the reference would pick a set of the strategies (include/fplll_hip.h).
+        transform: FPHIP_BKZ_TRANSFORM, as in bkz() (every variant above; slide_pass keeps refusing a tracked u).
         Returns (status[batch], info[batch][4])."""
         if prune_in_loop is not None:
             il = dict(preproc_cost=1e6, target=0.5, min_block=24, pruner_flags=0x4, on_device=True)
@@ -382,7 +388,8 @@ class MatGSOBatch:
         info = np.zeros((self.batch, 4), dtype=np.int32)
         flags = ((0x4 if max_loops > 0 else 0) | (0x80 if gh_bnd else 0) | (0x10 if bounded_lll else 0) |
                  (0x20 if auto_abort else 0) | (0x100 if sd else 0) | (0x1000 if handoff else 0) |
-                 (0x200 if slide else 0) | (0x2000 if prune_in_loop is not None else 0))
+                 (0x200 if slide else 0) | (0x2000 if prune_in_loop is not None else 0) |
+                 (_lib.FPHIP_BKZ_TRANSFORM if transform else 0))
         flags |= self._bkz_limits(max_time, dump_gso)  # BKZ_MAX_TIME / BKZ_DUMP_GSO
         rc = fn(self.h, block_size, delta, eta, flags, max_loops, gh_factor, sp, cb, rnd_user,
                 st.ctypes.data_as(ctypes.c_void_p), info.ctypes.data_as(ctypes.c_void_p))
@@ -465,6 +472,17 @@ class MatGSOBatch:
             raise NotImplementedError("block-parallel slide reduction needs BKZ_BOUNDED_LLL and blocks up to 64 rows")
         objects[0]._chk(rc, "slide_reduction_blocks")
         return st.value, nodes.value, tours.value
+
+    def bkz_insert_stats(self):
+        """fphip_gso_bkz_insert_stats (debug): the insertions of the last bkz() / bkz_strategies() call with
+        transform=True, summed over the batch — (one non-zero coefficient, a +-1 coefficient, primal gcd tree,
+        dual post-processing, row operations of rerandomize_block)."""
+        v = (ctypes.c_ulonglong * 5)()
+        fn = self.lib.fphip_gso_bkz_insert_stats
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]
+        self._chk(fn(self.h, v), "bkz_insert_stats")
+        return tuple(int(x) for x in v)
 
     def inloop_stats(self):
         """(prune() calls of the in-loop service, volume jobs on the device, inline on the host, launches)"""
@@ -676,6 +694,40 @@ def save_basis_txt(path, b):
         for i, row in enumerate(b):
             f.write(("" if i == 0 else "\n") + "[" + " ".join(str(int(v)) for v in row) + "]")
         f.write("]\n")
+
+
+def bkz_reduction(ctx, b, block_size, strategies=None, rnd=None, with_u=True, delta=LLL_DEF_DELTA, eta=LLL_DEF_ETA,
+                  max_loops=0, **bkz_options):
+    """bkz_reduction(b, u, param) (bkz.cpp:849-927) on the device: lll_reduction's lll() on a MatGSO(b, u, ...) with
+    u = identity, then BKZReduction::bkz() on the same object.  b: one basis [d][n] or a batch [batch][d][n].
+    strategies / rnd as MatGSOBatch.bkz_strategies (None, None: the empty strategies of MatGSOBatch.bkz);
+    bkz_options go to that entry point (auto_abort, gh_bnd, sd, slide, ...).  with_u=False skips the tracking.
+    Returns (b_out, u, status, info) — u None without with_u; u b = b_out in exact integers; for one basis the
+    leading batch axis is dropped.  The BKZ entry runs only when every lll() status is RED_SUCCESS (bkz.cpp:870-885
+    returns the failing lll status); otherwise status / info are lll()'s."""
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    single = b.ndim == 2
+    if single:
+        b = b[None]
+    g = MatGSOBatch(ctx, b.shape[0], b.shape[1], b.shape[2])
+    try:
+        g.set_basis(b)
+        if with_u:
+            g.enable_transform()
+        status, info = g.lll(delta=delta, eta=eta)
+        if all(int(s) == 1 for s in status):
+            if strategies is None and rnd is None and not bkz_options.keys() - {"auto_abort", "max_time", "dump_gso"}:
+                status, info = g.bkz(block_size, delta, eta, max_loops, transform=bool(with_u), **bkz_options)
+            else:
+                status, info = g.bkz_strategies(block_size, strategies, rnd, delta, eta, max_loops,
+                                                transform=bool(with_u), **bkz_options)
+        b_out = g.get_basis()
+        u = g.get_transform() if with_u else None
+    finally:
+        g.close()
+    if single:
+        return b_out[0], (None if u is None else u[0]), int(status[0]), info[0]
+    return b_out, u, status, info
 
 
 class BKZAutoAbort:

@@ -242,8 +242,9 @@ int fphip_gso_lll_flags(fphip_gso *g, int kappa_min, int kappa_start, int kappa_
  * fphip_gso_lll_flags apply every row operation to its rows as well and move them with b's (gso.cpp:84-158,
  * 289-366): afterwards u_out = T u_in with b_out = T b_in.  Sessions (below) keep u too: a dirty row is then its n
  * integers of b followed by its d integers of u, fphip_gso_session_read_transform returns u in position order.
- * While u is tracked the entry points that do not update it (size_reduce, bkz*, slide, lll_ex / ladder) return
- * FPHIP_UNSUPPORTED; fphip_gso_set_basis keeps u.  u_inv_t (enable_inverse_transform) is not offered. */
+ * While u is tracked the entry points that do not update it (size_reduce, bkz* without FPHIP_BKZ_TRANSFORM, slide,
+ * lll_ex / ladder) return FPHIP_UNSUPPORTED; fphip_gso_set_basis keeps u.  u_inv_t (enable_inverse_transform) is
+ * not offered. */
 int fphip_gso_enable_transform(fphip_gso *g, const int64_t *u);
 int fphip_gso_get_transform(fphip_gso *g, int first, int count, int64_t *u);
 /* The same lll() on a RESIDENT MatGSO: fplll's MatGSO is an object whose rows, Gram cache, mu / r and
@@ -275,8 +276,8 @@ int fphip_gso_session_read_transform(fphip_gso *g, int lattice, int64_t *u);
  * FastEvaluator(1)) on every lattice — primal BKZ with EMPTY strategies (no pruning, no
  * preprocessing: what bkz_reduction(b, beta, BKZ_DEFAULT, FT_DOUBLE) runs without a strategies
  * file, bkz_param.h:124-132), the whole reduction in one launch on device-resident GSO state.
- * flags: 0 (BKZ_DEFAULT), FPHIP_BKZ_MAX_LOOPS with max_loops, FPHIP_BKZ_AUTO_ABORT; block_size <= 64;
- * anything else
+ * flags: 0 (BKZ_DEFAULT), FPHIP_BKZ_MAX_LOOPS with max_loops, FPHIP_BKZ_AUTO_ABORT, FPHIP_BKZ_MAX_TIME,
+ * FPHIP_BKZ_DUMP_GSO, FPHIP_BKZ_TRANSFORM; block_size <= 64; anything else
  * returns FPHIP_UNSUPPORTED (the caller keeps fplll's CPU path).  The input must be LLL-reduced, as
  * bkz_reduction guarantees (bkz.cpp:870-885) — call fphip_gso_lll first.
  * status[batch]: 1 RED_SUCCESS, 8 RED_BKZ_LOOPS_LIMIT, <= 0 the failing LLL status.
@@ -289,6 +290,24 @@ int fphip_gso_session_read_transform(fphip_gso *g, int lattice, int64_t *u);
                                      one and the slope test runs on the host */
 int fphip_gso_bkz(fphip_gso *g, int block_size, double delta, double eta, int flags, int max_loops,
                   int *status, int *info);
+/* FPHIP_BKZ_TRANSFORM (not a flag of fplll: there it is MatGSO(b, u, ...) under bkz_reduction(b, u, param),
+ * bkz.cpp:849-927), for fphip_gso_bkz and fphip_gso_bkz_strategies: the run keeps the transformation matrix of
+ * fphip_gso_enable_transform in step with b — the row operations of LLL and size reduction inside the tours, the
+ * primal and dual insertions (svp_postprocessing, bkz.cpp:126-272), rerandomize_block (:43-80) — in kernels of their
+ * own (bkz_kernel_u, bkzs_kernel_u, bkzd_kernel_u); basis, status and info are those of the run without u.  Afterwards
+ * fphip_gso_get_transform returns u in position order: u_out b_in = b_out for a u that started as the identity,
+ * u_out = T u_in in general; also after a failing status.  Every other flag of the two entry points combines with
+ * it (FPHIP_BKZ_SD_VARIANT and FPHIP_BKZ_SLD_RED through fphip_gso_bkz_strategies included: one object).
+ * With the flag and no u tracked: FPHIP_ERROR (call fphip_gso_enable_transform first).  With u tracked and without
+ * the flag the entry points refuse as before (FPHIP_UNSUPPORTED).  fphip_gso_slide_pass and
+ * fphip_gso_slide_reduction_blocks refuse a tracked u with or without it: their tour merges rows of several
+ * objects, and moving u between contexts is not offered. */
+#define FPHIP_BKZ_TRANSFORM 0x4000
+/* Debug: the insertions of the last fphip_gso_bkz / fphip_gso_bkz_strategies call with FPHIP_BKZ_TRANSFORM, summed
+ * over the batch, by kind: counts[0] one non-zero coefficient (the row is only moved), [1] a +-1 coefficient
+ * (bkz.cpp:126-203), [2] the primal gcd tree (:205-272), [3] dual post-processing (any of the three, dual = true),
+ * [4] row additions / subtractions of rerandomize_block.  All zero when the last call ran without the flag. */
+int fphip_gso_bkz_insert_stats(const fphip_gso *g, unsigned long long counts[5]);
 /* BKZ WITH strategies: BKZReduction::bkz() with BKZParam(block_size, strategies, delta, flags,
  * max_loops, ..., gh_factor) — what bkz_reduction(b, beta, flags, FT_DOUBLE) runs with a strategies
  * file (BASELINE configs 3-4): recursive preprocessing tours (svp_preprocessing, bkz.cpp:100-124),
@@ -307,7 +326,7 @@ int fphip_gso_bkz(fphip_gso *g, int block_size, double delta, double eta, int fl
  * one a run of the reference on that lattice alone would draw from.
  * flags: FPHIP_BKZ_MAX_LOOPS, FPHIP_BKZ_BOUNDED_LLL, FPHIP_BKZ_AUTO_ABORT (one tour per launch, the
  * slope test on the host in between, as in fphip_gso_bkz), FPHIP_BKZ_GH_BND, FPHIP_BKZ_MAX_TIME,
- * FPHIP_BKZ_DUMP_GSO (fplll's values).
+ * FPHIP_BKZ_DUMP_GSO (fplll's values); FPHIP_BKZ_TRANSFORM (above).
  * FPHIP_BKZ_SD_VARIANT selects self-dual BKZ (sd_tour, dual svp_reduction / enumeration / insertion,
  * bkz.cpp:401-413,443-463; without MAX_LOOPS / AUTO_ABORT the auto abort is switched on, :548-554).
  * FPHIP_UNSUPPORTED: block sizes above 64, other flags, preprocessing nested deeper than 3 levels.
@@ -390,6 +409,8 @@ int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double delta, double 
  * fplll_amd.distributed.slide_reduction_blocks.  Every block is reduced from the PASS-START basis, whoever
  * reduces it, so the result does not depend on the number of devices; it is not the sequential reference's
  * (there block i sees block i - 1's new rows), and is accepted by the reference's predicates. */
+/* (A tracked transformation matrix is refused by both entry points below, FPHIP_BKZ_TRANSFORM or not: u does not
+ * travel between contexts.) */
 int fphip_gso_slide_pass(fphip_gso *g, int block_size, double delta, double eta, int flags, double gh_factor,
                          const fphip_strategies *S, fphip_rand_fn rnd, void *rnd_user, int pass,
                          unsigned long long block_mask, int *status, int *info);
