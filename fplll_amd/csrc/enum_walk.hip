@@ -9,7 +9,9 @@
 // (enumerate.cpp:218-239).  Same visit set, same arithmetic per node (separate multiply / add, the reference's
 // operand order), same per-level counts and candidates as enum_phase_kernel (enum_kernel.hip) — which stays the
 // kernel of the split launches, of sub-solution calls and the A/B partner of these (FPHIP_WALK2=0).  The final walk
-// launches run the third generation; FPHIP_WALK3=0 selects the second, its A/B partner.
+// launches of shortest-vector calls run the fourth generation (this text a third time, under FPHIP_WALK4: see
+// enum_walk4.hip and the macros below), closest-vector calls and FPHIP_WALK4=0 the third; FPHIP_WALK3=0 selects the
+// second, its A/B partner.
 //
 // The second generation: what changed, and why.  enum_phase_kernel visits the children of a node one test at a
 // time: the first child in its CHILD chain, every later sibling in its STEP loop, and every node's sibling sequence
@@ -90,6 +92,20 @@
 #else
 #define FPHIP_WALK_KERNEL enum_walk_kernel
 #endif
+// The fourth generation (enum_walk4.hip compiles this text with FPHIP_WALK4 = 1 into enum_walk4_kernel<MU_LDS, DUAL>,
+// see the header there): the third with ready pair siblings.  Every line of it sits behind the preprocessor
+// (FPHIP_W4_PAIR): without the macro the text, and with it the machine code of the kernels above, is what it was
+// (tests/perf/walk_isa_diff.py).
+#ifndef FPHIP_WALK4
+#define FPHIP_WALK4 0
+#endif
+#if FPHIP_WALK4
+#undef FPHIP_WALK_KERNEL
+#define FPHIP_WALK_KERNEL enum_walk4_kernel
+#define FPHIP_W4_PAIR 1
+#else
+#define FPHIP_W4_PAIR 0
+#endif
 
 namespace fphip
 {
@@ -127,7 +143,11 @@ __device__ __forceinline__ v2u r_issue(const double *tab, unsigned off)
 __device__ __forceinline__ void rp_wait(v2u &q) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(q)); }
 __device__ __forceinline__ double rp_r2(const v2u &q) { return __hiloint2double((int)q.y, (int)q.x); }
 
+#if FPHIP_WALK4
+template <bool MU_LDS, bool DUAL>
+#else
 template <bool MU_LDS, bool DUAL, bool CHAIN>
+#endif
 __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
     FPHIP_WALK_KERNEL(DevShared *__restrict__ g, HostCtl *__restrict__ h, TaskBuf in, TaskBuf out,
                      int d, int Lmax, unsigned task_lo, unsigned task_hi,
@@ -137,6 +157,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
                      unsigned long long bound_init)
 {
   constexpr bool CVP = FPHIP_CVP != 0;  // closest-vector mode: see the header
+#if FPHIP_WALK4
+  constexpr bool CHAIN = true;
+#endif
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (wave-uniform: the per-wave bases in SGPRs)
@@ -302,6 +325,14 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       zc = false;  // (!is_svp, :80: no zero chain — the root expands as a zig-zag like every other node)
     // CHAIN: the sibling masks (see the header): the task root's level holds no sibling, an empty P ends the task
     unsigned long long P = 0ull, B = 0ull;
+#if FPHIP_W4_PAIR
+    // Q  level l is a pair level (its expansion had exactly two children).  With P: the pending sibling is READY — its
+    //    column sits in the level's stack slot, its distance in lane l of pds, its coefficient in lane l of x0s; B is
+    //    clear while the walk is below the first child (coefficient roundto(centre), as for any level outside B).  With
+    //    B: the walk is below the second child, whose coefficient is lane l of x0s (cs and st of the lane are stale).
+    //    Every place that sets P or B of a level defines its Q; a Q bit with neither is never read.
+    unsigned long long Q = 0ull;
+#endif
     // else: the climb that reaches the root's level ends the task: a slow marker in its lane (lane 0 when Lt = 64 —
     // level 0 keeps no sibling state: its nodes are the leaf loop's)
     if constexpr (!CHAIN)
@@ -331,6 +362,11 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
         {
           const double c = rl_f64(Sr, l);
           double x;
+#if FPHIP_W4_PAIR
+          if ((B >> l) & (Q >> l) & 1ull)
+            x = rl_f64(x0s, l);  // (the second child of a pair level: stored as it was formed)
+          else
+#endif
           if ((B >> l) & 1ull)
           {
             const int s_    = rl_i32(st, l);
@@ -412,7 +448,11 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
     auto reprune = [&](int klo)
     {
       int s_           = st;
+#if FPHIP_W4_PAIR  // (a pair level keeps no (c, x_0, st): its pending sibling is tested below)
+      const bool act   = lane >= klo && lane < Lt && (((B & ~Q) >> lane) & 1ull) != 0ull && !ST_IS_SLOW(s_);
+#else
       const bool act   = lane >= klo && lane < Lt && (!CHAIN || ((B >> lane) & 1ull) != 0ull) && !ST_IS_SLOW(s_);
+#endif
       const double r_l = g->rdiag[lane];
       const double b_l = g->pruning[lane] * maxdist;
       const int cur    = ST_I(s_);
@@ -434,6 +474,14 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       st = act ? s_ : st;
       if constexpr (CHAIN)
         P &= ~__builtin_amdgcn_ballot_w64(act && cur + 1 >= n);
+#if FPHIP_W4_PAIR
+      {  // the ready sibling of a pair level: its distance is lane l of pds, formed at the descent
+        const bool pend = lane >= klo && lane < Lt && (((P & Q) >> lane) & 1ull) != 0ull;
+        const unsigned long long gone = __builtin_amdgcn_ballot_w64(pend && !(pds <= b_l));
+        P &= ~gone;
+        Q &= ~gone;
+      }
+#endif
       FPHIP_JOIN();
     };
 
@@ -562,6 +610,31 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               // -a1 where fix (the operand of the dual column update), as a flip of the sign bit in place
               a1 = __hiloint2double(__double2hiint(a1) ^ (fix ? (int)0x80000000 : 0), __double2loint(a1));
             }
+#if FPHIP_W4_PAIR
+            if (c == 5)
+            {  // exactly two children: the sibling is formed HERE, where its operands are in registers, by the
+               // operations, operands and order of STEP (see the header of enum_walk4.hip) — its column goes into the
+               // slot of the push, its distance and coefficient into lane kc of pds and x0s; nothing else is kept
+              const double sd  = __hiloint2double((c1 >= x1) ? 0x3ff00000 : (int)0xbff00000, 0);
+              const double x2  = x1 + sd;
+              const double a2  = x2 - c1;
+              const double nd2 = nd + a2 * a2 * rp_r(q1);
+              const double S1  = S - (DUAL ? a1 : x1) * mk1;
+              S                = S - (DUAL ? a2 : x2) * mk1;
+              FPHIP_PUSH(kc < Ts - 1, kc + 1, tri8(kc + 2));
+              P |= me;
+              Q |= me;
+              B &= ~me;
+              x0s = sel_f64(me, x2, x0s);
+              pds = sel_f64(me, nd2, pds);
+              cnt32 = add_bit(me, cnt32);
+              nd    = row_bcast0_f64(ndj);
+              S  = S1;
+              --kc;
+              continue;
+            }
+            Q &= ~me;
+#endif
             // (CHAIN: siblings follow) S_k is needed again when x[kc] steps to a sibling
             FPHIP_PUSH(kc < Ts - 1, kc + 1, tri8(kc + 2));
             if constexpr (CHAIN)
@@ -597,6 +670,30 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           }
           k  = __builtin_ctzll(P);
           ka = lane_addr(k);
+#if FPHIP_W4_PAIR
+          if ((Q >> k) & 1ull)
+          {  // ================= pair STEP: the sibling is ready — pop its column, fetch its distance ====
+            if (__builtin_expect(--left < 0, 0))
+            {
+              ev = EV_REFRESH;
+              break;
+            }
+            const unsigned long long me = lane_bit(k);
+            P &= ~me;
+            B |= me;  // (with Q: the level's coefficient is lane k of x0s)
+            if (__builtin_expect(k < Tsm1, 1))
+              S = *(const double *)(stk_top - tri8(k + 2));
+            else
+            {
+              int kt = k;
+              asm volatile("" : "+s"(kt));
+              S = ld_off(gst, tri8(kt + 1) + min(lane8, ((unsigned)kt << 3) - 8u));
+            }
+            nd = bp_f64(pds, ka);
+            cnt32 = add_bit(me, cnt32);  // ++nodes[kk]
+            continue;
+          }
+#endif
           tk = rl_i32(st, k) + 1;
         }
         else
@@ -746,6 +843,9 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             P |= lane_bit(kc);
             B |= lane_bit(kc);
           }
+#if FPHIP_W4_PAIR
+          Q &= ~lane_bit(kc);
+#endif
           cs  = (lane == kc) ? c1 : cs;
           x0s = (lane == kc) ? x1 : x0s;
           pds = (lane == kc) ? nd : pds;
@@ -872,6 +972,18 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
     atomicAdd(&g->iters, (unsigned long long)iter);
 }
 
+#if FPHIP_WALK4
+#define FPHIP_INST4(M, D)                                                                            \
+  template __global__ void FPHIP_WALK_KERNEL<M, D>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int, \
+                                                  unsigned, unsigned, const unsigned *, int, int,       \
+                                                  unsigned, const double *, double *, int, unsigned *,   \
+                                                  const unsigned *, unsigned, unsigned long long);
+FPHIP_INST4(true, false)
+FPHIP_INST4(false, false)
+FPHIP_INST4(true, true)
+FPHIP_INST4(false, true)
+#undef FPHIP_INST4
+#else
 #define FPHIP_INST(M, D, C)                                                                             \
   template __global__ void FPHIP_WALK_KERNEL<M, D, C>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int, \
                                                   unsigned, unsigned, const unsigned *, int, int,       \
@@ -890,5 +1002,6 @@ FPHIP_INST(true, true, true)
 FPHIP_INST(false, true, true)
 #endif
 #undef FPHIP_INST
+#endif
 
 }  // namespace fphip
