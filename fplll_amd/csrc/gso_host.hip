@@ -73,6 +73,8 @@ __global__ void bkzd_kernel_u(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abo
                               int stack_doubles, int run_mode, unsigned long long *ustats);
 }
 template <int NQ> __global__ void hlll_kernel(HhBatch P, double delta, double theta, long long iter_cap);
+template <int NQ>
+__global__ void hlll_u_kernel(HhBatch P, double delta, double theta, long long iter_cap, long long *Uall, int ldu);
 template <int NQ> __global__ void hh_blocked_kernel(HhBatch P, double *Tbuf);
 struct HlllX
 {
@@ -86,6 +88,7 @@ struct HlllX
   double *Rx, *Vx;
 };
 template <int NQ, class FT> __global__ void hlll_x_kernel(HhBatch P, HlllX X);
+template <int NQ, class FT> __global__ void hlll_x_u_kernel(HhBatch P, HlllX X, long long *Uall, int ldu);
 struct LllX
 {
   int batch, d, n, ldn, ldd, row_expo;
@@ -3043,6 +3046,7 @@ namespace fphip
 template <int NQ> __global__ void hh_update_kernel(HhBatch P);
 template <int NT> __global__ void hh_rows_kernel(HhBatch P);
 __global__ void hh_size_reduce_kernel(HhBatch P, int k, int end, int start, int *reduced);
+__global__ void hh_size_reduce_u_kernel(HhBatch P, int k, int end, int start, int *reduced, long long *Uall, int ldu);
 }
 
 struct fphip_hh
@@ -3058,6 +3062,10 @@ struct fphip_hh
   double *xThi = nullptr, *xTlo = nullptr;  // hlll_x: T of every block of 16 reflectors (blocked application)
   double *xRx = nullptr, *xVx = nullptr;    // hlll_x in quad-double: components 2 and 3 of R and V
   int x_planes = 0;                         // component planes of R the last fphip_hh_hlll_ex run wrote (0: none yet)
+  // the transformation matrix (fphip_hh_enable_transform), [batch][d][ldu]; null = not tracked.  Kept out of HhBatch:
+  // that struct is a by-value argument of every Householder kernel, the u kernels take the two as extra parameters
+  long long *u = nullptr;
+  int ldu      = 0;
 };
 
 #define HCHK(call)                     \
@@ -3159,6 +3167,8 @@ extern "C" void fphip_hh_destroy(fphip_hh *h)
     fphip_dev_free(h->xRx, fphip_ctx_stream(h->ctx));
   if (h->xVx)
     fphip_dev_free(h->xVx, fphip_ctx_stream(h->ctx));
+  if (h->u)
+    fphip_dev_free(h->u, fphip_ctx_stream(h->ctx));
   delete h;
 }
 
@@ -3182,7 +3192,72 @@ extern "C" int fphip_hh_broadcast_basis(fphip_hh *h, int src)
     if (L != src)
       HCHK(hipMemcpyAsync(h->P.b + (size_t)L * per, h->P.b + (size_t)src * per, per * 8,
                           hipMemcpyDeviceToDevice, fphip_ctx_stream(h->ctx)));
+  if (h->u)
+  {  // MatHouseholder(b, u, ...): the copies start from src's pair
+    const size_t peru = (size_t)h->P.d * h->ldu;
+    for (int L = 0; L < h->P.batch; ++L)
+      if (L != src)
+        HCHK(hipMemcpyAsync(h->u + (size_t)L * peru, h->u + (size_t)src * peru, peru * 8, hipMemcpyDeviceToDevice,
+                            fphip_ctx_stream(h->ctx)));
+  }
   HCHK(hipStreamSynchronize(fphip_ctx_stream(h->ctx)));
+  return FPHIP_OK;
+}
+
+// MatHouseholder(b, u, u_inv, flags) with a non-empty u (householder.h:70-130): the transformation matrix on the
+// device, [batch][d][ldu] with ldu padded like ldn.  From here on fphip_hh_hlll, fphip_hh_hlll_ex, fphip_hh_hlll_ladder
+// and fphip_hh_size_reduce launch the u-carrying forms of their kernels (hlll_kernel_u.hip, hlll_x_u.hip,
+// hh_size_reduce_u_kernel), which apply row_addmul_we (householder.cpp:522-559) and swap (:372-398) to u as to b.
+// u = NULL: the identity.  A second call resets u.
+extern "C" int fphip_hh_enable_transform(fphip_hh *h, const int64_t *u)
+{
+  if (!h)
+    return FPHIP_ERROR;
+  if (h->P.d > h->P.n)
+  {  // the kernels' columns-per-lane count follows n alone; a row of u has d entries
+    snprintf(fphip_ctx_errbuf(h->ctx), 512,
+             "fphip_hh_enable_transform: d = %d rows exceed n = %d columns; the transformation matrix is carried for "
+             "d <= n only", h->P.d, h->P.n);
+    return FPHIP_UNSUPPORTED;
+  }
+  const size_t B = (size_t)h->P.batch, d = h->P.d;
+  hipStream_t s  = fphip_ctx_stream(h->ctx);
+  if (!h->u)
+  {
+    int ldu = (h->P.d + 15) / 16 * 16;
+    if (ldu > 256)
+      ldu = 256;
+    HCHK(fphip_dev_alloc((void **)&h->u, B * d * (size_t)ldu * sizeof(long long) + 4096, s));
+    h->ldu = ldu;
+  }
+  const size_t ldu = h->ldu;
+  HCHK(hipMemsetAsync(h->u, 0, B * d * ldu * sizeof(long long) + 4096, s));
+  HCHK(hipStreamSynchronize(s));
+  if (u)
+    HCHK(hipMemcpy2D(h->u, ldu * 8, u, d * 8, d * 8, B * d, hipMemcpyHostToDevice));
+  else
+  {
+    std::vector<long long> id(d * ldu, 0);
+    for (size_t i = 0; i < d; ++i)
+      id[i * ldu + i] = 1;
+    for (size_t L = 0; L < B; ++L)
+      HCHK(hipMemcpy(h->u + L * d * ldu, id.data(), d * ldu * sizeof(long long), hipMemcpyHostToDevice));
+  }
+  HCHK(hipStreamSynchronize(nullptr));  // (see fphip_gso_set_basis)
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_hh_get_transform(fphip_hh *h, int first, int count, int64_t *u)
+{
+  if (!h || !u || first < 0 || count <= 0 || first + count > h->P.batch)
+    return FPHIP_ERROR;
+  if (!h->u)
+  {
+    snprintf(fphip_ctx_errbuf(h->ctx), 512, "fphip_hh_get_transform: no transformation matrix (fphip_hh_enable_transform)");
+    return FPHIP_ERROR;
+  }
+  const size_t d = h->P.d, ldu = h->ldu;
+  HCHK(hipMemcpy2D(u, d * 8, h->u + (size_t)first * d * ldu, ldu * 8, d * 8, d * (size_t)count, hipMemcpyDeviceToHost));
   return FPHIP_OK;
 }
 
@@ -3258,6 +3333,10 @@ extern "C" int fphip_hh_size_reduce(fphip_hh *h, int kappa, int size_reduction_e
   int *dred     = nullptr;
   HCHK(fphip_dev_alloc((void **)&dred, sizeof(int) * (size_t)h->P.batch, s));
   HCHK(hipEventRecord(h->ev[0], s));
+  if (h->u)
+    hipLaunchKernelGGL(hh_size_reduce_u_kernel, dim3((h->P.batch + 3) / 4), dim3(256), 0, s, h->P, kappa,
+                       size_reduction_end, size_reduction_start, dred, h->u, h->ldu);
+  else
   hipLaunchKernelGGL(hh_size_reduce_kernel, dim3((h->P.batch + 3) / 4), dim3(256), 0, s, h->P, kappa,
                      size_reduction_end, size_reduction_start, dred);
   hipError_t le = hipGetLastError();
@@ -3356,6 +3435,15 @@ extern "C" int fphip_hh_hlll(fphip_hh *h, double delta, double eta, double theta
   const long long cap = 1LL << 40;
   hipStream_t s = fphip_ctx_stream(h->ctx);
   HCHK(hipEventRecord(h->ev[0], s));
+  if (h->u)  // the transformation matrix is tracked: the u-carrying kernel (hlll_kernel_u.hip), same launch shape
+    switch (nq)
+    {
+    case 1: hipLaunchKernelGGL(hlll_u_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
+    case 2: hipLaunchKernelGGL(hlll_u_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
+    case 3: hipLaunchKernelGGL(hlll_u_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
+    default: hipLaunchKernelGGL(hlll_u_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
+    }
+  else
   switch (nq)
   {
   case 1: hipLaunchKernelGGL(hlll_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap); break;
@@ -3463,7 +3551,34 @@ static int hh_hlll_ex(fphip_hh *h, double delta, double theta, int precision, co
     grid = fphip_ctx_num_cus(h->ctx) * 8;
   hipStream_t s = fphip_ctx_stream(h->ctx);
   HCHK(hipEventRecord(h->ev[0], s));
-  if (precision == 212)
+  if (h->u)  // the transformation matrix is tracked: the u-carrying kernels (hlll_x_u.hip)
+  {
+    if (precision == 212)
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL((hlll_x_u_kernel<1, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      case 2: hipLaunchKernelGGL((hlll_x_u_kernel<2, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      case 3: hipLaunchKernelGGL((hlll_x_u_kernel<3, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      default: hipLaunchKernelGGL((hlll_x_u_kernel<4, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      }
+    else if (precision == 106)
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL((hlll_x_u_kernel<1, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      case 2: hipLaunchKernelGGL((hlll_x_u_kernel<2, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      case 3: hipLaunchKernelGGL((hlll_x_u_kernel<3, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      default: hipLaunchKernelGGL((hlll_x_u_kernel<4, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      }
+    else
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL((hlll_x_u_kernel<1, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      case 2: hipLaunchKernelGGL((hlll_x_u_kernel<2, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      case 3: hipLaunchKernelGGL((hlll_x_u_kernel<3, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      default: hipLaunchKernelGGL((hlll_x_u_kernel<4, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
+      }
+  }
+  else if (precision == 212)
     switch (nq)
     {
     case 1: hipLaunchKernelGGL((hlll_x_kernel<1, QD>), dim3(grid), dim3(64), 0, s, h->P, X); break;

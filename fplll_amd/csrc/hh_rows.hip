@@ -336,7 +336,13 @@ __device__ __forceinline__ long long hsr_fexponent(double x)
   return (x == 0.0) ? ((long long)INT_MIN + 1) : ((long long)ilogb(x) + 1);
 }
 
-__global__ void __launch_bounds__(256) hh_size_reduce_kernel(HhBatch P, int k, int end, int start, int *reduced)
+//
+// WITH_U (hh_size_reduce_u_kernel, fphip_hh_enable_transform): row_addmul_we's integer AXPY on the transformation
+// matrix as well (householder.cpp:536-557: u[k] += lx u[i], [d][ldu] row-major per lattice, lane = column), summed in
+// registers and stored where b[k] is, so an untouched lattice keeps its u.  Compiled out of the plain kernel.
+template <bool WITH_U>
+__device__ __forceinline__ void hh_size_reduce_body(const HhBatch &P, int k, int end, int start, int *reduced,
+                                                    long long *Uall, int ldu)
 {
   const int lane = threadIdx.x & 63;
   const int lat  = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -354,6 +360,18 @@ __global__ void __launch_bounds__(256) hh_size_reduce_kernel(HhBatch P, int k, i
     const int c = lane + 64 * q;
     Rk[q]       = (c < n) ? R[(size_t)k * ld + c] : 0.0;
     bk[q]       = (c < n) ? b[(size_t)k * ld + c] : 0;
+  }
+  long long *u = nullptr;
+  long long uk[4];
+  if constexpr (WITH_U)
+  {
+    u = Uall + (size_t)lat * d * ldu;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+    {
+      const int c = lane + 64 * q;
+      uk[q]       = (c < d) ? u[(size_t)k * ldu + c] : 0;
+    }
   }
   const long long rxk = rx[k];
   int red             = 0;
@@ -393,6 +411,12 @@ __global__ void __launch_bounds__(256) hh_size_reduce_kernel(HhBatch P, int k, i
             Rk[q]          = Rk[q] + t;
           }
         }
+        if constexpr (WITH_U)
+        {
+          if (c < d)
+            uk[q] = (long long)((unsigned long long)uk[q] +
+                                (unsigned long long)u[(size_t)i * ldu + c] * (unsigned long long)lx);
+        }
       }
       red = 1;
     }
@@ -416,12 +440,28 @@ __global__ void __launch_bounds__(256) hh_size_reduce_kernel(HhBatch P, int k, i
       if (c < k)
         R[(size_t)k * ld + c] = Rk[q];
     }
+    if constexpr (WITH_U)
+    {
+      if (c < d && red)
+        u[(size_t)k * ldu + c] = uk[q];
+    }
   }
   if (lane == 0)
   {
     P.status[lat] = 1;
     reduced[lat]  = red;
   }
+}
+
+__global__ void __launch_bounds__(256) hh_size_reduce_kernel(HhBatch P, int k, int end, int start, int *reduced)
+{
+  hh_size_reduce_body<false>(P, k, end, start, reduced, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(256)
+    hh_size_reduce_u_kernel(HhBatch P, int k, int end, int start, int *reduced, long long *Uall, int ldu)
+{
+  hh_size_reduce_body<true>(P, k, end, start, reduced, Uall, ldu);
 }
 
 template __global__ void hh_rows_kernel<4>(HhBatch);

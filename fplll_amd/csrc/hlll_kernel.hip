@@ -22,8 +22,24 @@
 // dot products are the reference's sequential sums (v_readlane chains, seq_sum), AXPYs are plain
 // vector operations; reflectors V_j and the rows R_i / b_i of the size reduction are streamed
 // through the LDS-DMA ring.
+//
+// FPHIP_HLLL_U (hlll_kernel_u.hip): the same text compiled as hlll_u_kernel<NQ>, which carries the transformation
+// matrix u of MatHouseholder(b, u, ...) (fphip_hh_enable_transform): u is [d][ldu] row-major per lattice, lane =
+// column like b, and takes the two row operations hlll.cpp applies to b — row_addmul_we (householder.cpp:522-559:
+// u[k] += lx u[i], wrapped like Z_NR<long>) and swap (:372-398).  The rows u_i of a size reduction follow the rows
+// b_i through the ring as a third phase with the same multipliers; the sum is added to u[k] where b[k] is stored,
+// so a lattice that stops on a multiplier beyond 63 bits keeps the u of the b it keeps.  Without the macro every
+// line of it is compiled out: hlll_kernel<NQ> is the output of its own translation unit, as before.
 
 #include "gso_wave.h"
+
+#ifdef FPHIP_HLLL_U
+#define FPHIP_HLLL_KERNEL hlll_u_kernel
+#define FPHIP_HLLL_UARGS , long long *Uall, int ldu
+#else
+#define FPHIP_HLLL_KERNEL hlll_kernel
+#define FPHIP_HLLL_UARGS
+#endif
 
 namespace fphip
 {
@@ -60,7 +76,7 @@ template <int NQ> __device__ __forceinline__ void hl_seti(int (&v)[NQ], int idx,
 // info[2] per lattice: swaps, loop iterations
 template <int NQ>
 __global__ void __launch_bounds__(256)
-    hlll_kernel(HhBatch P, double delta, double theta, long long iter_cap)
+    FPHIP_HLLL_KERNEL(HhBatch P, double delta, double theta, long long iter_cap FPHIP_HLLL_UARGS)
 {
   constexpr int IPS = (NQ + 1) / 2;
   extern __shared__ __attribute__((aligned(16))) char hlll_smem[];
@@ -81,6 +97,9 @@ __global__ void __launch_bounds__(256)
     double *R       = P.R + (size_t)L * d * ld;
     double *sigma   = P.sigma + (size_t)L * d;
     long long *rexp = P.rexp + (size_t)L * d;
+#ifdef FPHIP_HLLL_U
+    long long *u = Uall + (size_t)L * d * ldu;
+#endif
     // per-row scalars, lane i (chunk q) = row i + 64 q
     double sg[NQ], rd[NQ], nsb[NQ], dR[NQ], eR[NQ], prevR[NQ];
     int rx[NQ], prevE[NQ];
@@ -322,6 +341,9 @@ __global__ void __launch_bounds__(256)
             return RowDesc{R + (size_t)i * ld, 0, i * 8};  // R(i, c) is needed for c < i
           };
           auto b_row = [&](int s) { return RowDesc{b + (size_t)(itop - s) * ld, 0, n * 8}; };
+#ifdef FPHIP_HLLL_U
+          auto u_row = [&](int s) { return RowDesc{u + (size_t)(itop - s) * ldu, 0, d * 8}; };
+#endif
 #pragma unroll
           for (int q = 0; q < NQ; ++q)
           {
@@ -384,7 +406,38 @@ __global__ void __launch_bounds__(256)
                                                                       (unsigned long long)lx);
                                           }
                                         });
+                   }
+#ifdef FPHIP_HLLL_U
+                   ,
+                   cnt, u_row
+#endif
+          );
+#ifdef FPHIP_HLLL_U
+          // the same pass over the rows of u: uv = sum lx_i u_i (rows i < k are fixed during the pass, and the order
+          // of the terms does not matter in wrapped arithmetic); u[k] itself is read where it is written, below
+          long long uv[NQ];
+#pragma unroll
+          for (int q = 0; q < NQ; ++q)
+            uv[q] = 0;
+          ring.run(cnt, u_row,
+                   [&](int s, const double(&v)[NQ])
+                   {
+                     const int i = itop - s;
+                     dispatch_chunk<NQ>(i,
+                                        [&](auto iq_, int ii)
+                                        {
+                                          const long long lx = g_rl_i64(xl[decltype(iq_)::value], ii);
+                                          if (lx != 0)
+                                          {
+#pragma unroll
+                                            for (int q = 0; q < NQ; ++q)
+                                              uv[q] = (long long)((unsigned long long)uv[q] +
+                                                                  (unsigned long long)__double_as_longlong(v[q]) *
+                                                                      (unsigned long long)lx);
+                                          }
+                                        });
                    });
+#endif
           if (too_big)
           {
             status = -2;
@@ -397,6 +450,15 @@ __global__ void __launch_bounds__(256)
             if (c < n)
               b[(size_t)k * ld + c] = bv[q];
           }
+#ifdef FPHIP_HLLL_U
+#pragma unroll
+          for (int q = 0; q < NQ; ++q)
+          {
+            const int c = lane + 64 * q;
+            if (c < d)
+              u[(size_t)k * ldu + c] = (long long)((unsigned long long)u[(size_t)k * ldu + c] + (unsigned long long)uv[q]);
+          }
+#endif
           // ---- hlll.cpp:318-349: t = old ||b_k||^2, refresh, compare, update_R again
           const double told = hl_get<NQ>(nsb, k);
           const int e0      = P.row_expo ? 2 * rxk : 0;
@@ -523,6 +585,19 @@ __global__ void __launch_bounds__(256)
               bf[(size_t)k * ld + c]       = fa[q];
             }
           }
+#ifdef FPHIP_HLLL_U
+#pragma unroll
+          for (int q = 0; q < NQ; ++q)
+          {
+            const int c = lane + 64 * q;
+            if (c < d)
+            {
+              const long long ua = u[(size_t)(k - 1) * ldu + c], ub = u[(size_t)k * ldu + c];
+              u[(size_t)(k - 1) * ldu + c] = ub;
+              u[(size_t)k * ldu + c]       = ua;
+            }
+          }
+#endif
           const int ea = hl_geti<NQ>(rx, k - 1), eb = hl_geti<NQ>(rx, k);
           hl_seti<NQ>(rx, k - 1, eb, lane);
           hl_seti<NQ>(rx, k, ea, lane);
@@ -567,9 +642,16 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+#ifdef FPHIP_HLLL_U
+template __global__ void hlll_u_kernel<1>(HhBatch, double, double, long long, long long *, int);
+template __global__ void hlll_u_kernel<2>(HhBatch, double, double, long long, long long *, int);
+template __global__ void hlll_u_kernel<3>(HhBatch, double, double, long long, long long *, int);
+template __global__ void hlll_u_kernel<4>(HhBatch, double, double, long long, long long *, int);
+#else
 template __global__ void hlll_kernel<1>(HhBatch, double, double, long long);
 template __global__ void hlll_kernel<2>(HhBatch, double, double, long long);
 template __global__ void hlll_kernel<3>(HhBatch, double, double, long long);
 template __global__ void hlll_kernel<4>(HhBatch, double, double, long long);
+#endif
 
 }  // namespace fphip

@@ -19,8 +19,22 @@
 // One wavefront per lattice, lane = column (NQ per lane); the working row R[k] stays in registers;
 // size_reduce evaluates every candidate multiplier of the row at once (lane i: R(k,i)/R(i,i)) and
 // applies the highest non-zero one, so its cost follows the number of row operations, not k.
+//
+// FPHIP_HLLL_X_U (hlll_x_u.hip): the same text compiled as hlll_x_u_kernel<NQ, FT>, which carries the transformation
+// matrix u (fphip_hh_enable_transform; [d][ldu] row-major per lattice, lane = column): row_addmul_we's integer AXPY
+// and swap's row exchange run on u next to b, statement for statement, so u describes the b on the device whatever
+// the status (a multiplier beyond 63 bits returns before either row is touched).  Without the macro every line of
+// it is compiled out, and the unit-test kernels below belong to this translation unit alone.
 #include "ftx.h"
 #include "gso_device.h"
+
+#ifdef FPHIP_HLLL_X_U
+#define FPHIP_HLLL_X_KERNEL hlll_x_u_kernel
+#define FPHIP_HLLL_X_UARGS , long long *Uall, int ldu
+#else
+#define FPHIP_HLLL_X_KERNEL hlll_x_kernel
+#define FPHIP_HLLL_X_UARGS
+#endif
 
 namespace fphip
 {
@@ -75,7 +89,8 @@ struct HlllX
 
 // status: 1 RED_SUCCESS, -2 multiplier beyond 63 bits, -4 RED_HLLL_SR_FAILURE,
 //         -5 RED_HLLL_NORM_FAILURE, -6 iteration cap.  info[2] per lattice: swaps, loop iterations
-template <int NQ, class FT> __global__ void __launch_bounds__(64) hlll_x_kernel(HhBatch P, HlllX X)
+template <int NQ, class FT>
+__global__ void __launch_bounds__(64) FPHIP_HLLL_X_KERNEL(HhBatch P, HlllX X FPHIP_HLLL_X_UARGS)
 {
   const int lane = threadIdx.x & 63;
   const int d = P.d, n = P.n, ld = P.ldn;
@@ -88,6 +103,9 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) hlll_x_kernel(
     double *bf      = P.bf + (size_t)L * d * ld;
     double *sigma   = P.sigma + (size_t)L * d;
     long long *rexp = P.rexp + (size_t)L * d;
+#ifdef FPHIP_HLLL_X_U
+    long long *u = Uall + (size_t)L * d * ldu;
+#endif
     const size_t pl = (size_t)P.batch * d * ld, lo0 = (size_t)L * d * ld;
     const Plane<FT> R{P.R + lo0, X.Rlo ? X.Rlo + lo0 : nullptr, X.Rx ? X.Rx + lo0 : nullptr, X.Rx ? X.Rx + pl + lo0 : nullptr};
     const Plane<FT> V{P.V + lo0, X.Vlo ? X.Vlo + lo0 : nullptr, X.Vx ? X.Vx + lo0 : nullptr, X.Vx ? X.Vx + pl + lo0 : nullptr};
@@ -456,6 +474,13 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) hlll_x_kernel(
             if (c < top)
               Rk[q] = f_add(Rk[q], f_mul(R.ld(it), x));
           }
+#ifdef FPHIP_HLLL_X_U
+          if (c < d)
+          {
+            const size_t ik = (size_t)k * ldu + c, it = (size_t)top * ldu + c;
+            u[ik]           = (long long)((unsigned long long)u[ik] + (unsigned long long)u[it] * (unsigned long long)lx);
+          }
+#endif
         }
         limit   = top;
         reduced = 1;
@@ -618,6 +643,15 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) hlll_x_kernel(
               bf[i0]             = bf[i1];
               bf[i1]             = tf;
             }
+#ifdef FPHIP_HLLL_X_U
+            if (c < d)
+            {
+              const size_t i0 = (size_t)(k - 1) * ldu + c, i1 = (size_t)k * ldu + c;
+              const long long tu = u[i0];
+              u[i0]              = u[i1];
+              u[i1]              = tu;
+            }
+#endif
           }
           if (lane == 0)
           {
@@ -658,6 +692,20 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) hlll_x_kernel(
   }
 }
 
+#ifdef FPHIP_HLLL_X_U
+template __global__ void hlll_x_u_kernel<1, double>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<2, double>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<3, double>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<4, double>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<1, DD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<2, DD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<3, DD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<4, DD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<1, QD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<2, QD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<3, QD>(HhBatch, HlllX, long long *, int);
+template __global__ void hlll_x_u_kernel<4, QD>(HhBatch, HlllX, long long *, int);
+#else
 template __global__ void hlll_x_kernel<1, double>(HhBatch, HlllX);
 template __global__ void hlll_x_kernel<2, double>(HhBatch, HlllX);
 template __global__ void hlll_x_kernel<3, double>(HhBatch, HlllX);
@@ -759,5 +807,7 @@ __global__ void __launch_bounds__(256) ftx_op_kernel(const double *pa, const dou
 }
 template __global__ void ftx_op_kernel<DD>(const double *, const double *, double *, int, int);
 template __global__ void ftx_op_kernel<QD>(const double *, const double *, double *, int, int);
+
+#endif  // FPHIP_HLLL_X_U
 
 }  // namespace fphip

@@ -72,6 +72,41 @@ class MatHouseholderBatch:
     def broadcast_basis(self, src=0):
         self._chk(self.lib.fphip_hh_broadcast_basis(self.h, src), "broadcast_basis")
 
+    def enable_transform(self, u=None):
+        """MatHouseholder(b, u, u_inv, flags) with a non-empty u: track the transformation matrix on the device —
+        u [batch][d][d] int64, or None for the identity.  hlll() at every precision, hlll_ladder() and size_reduce()
+        then apply every row operation to u as well (householder.cpp:372-398, 456-559); update_R() does not touch b.
+        set_basis() keeps u, broadcast_basis() copies it with b, a second call resets it.  Needs d <= n."""
+        fn = self.lib.fphip_hh_enable_transform
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.int64)
+            assert u.shape == (self.batch, self.d, self.d)
+        rc = fn(self.h, None if u is None else u.ctypes.data_as(ctypes.c_void_p))
+        if rc == _lib.FPHIP_UNSUPPORTED:
+            raise NotImplementedError("enable_transform: " + self.ctx.last_error())
+        self._chk(rc, "enable_transform")
+
+    def get_transform(self, first=0, count=None):
+        count = self.batch - first if count is None else count
+        u = np.empty((count, self.d, self.d), dtype=np.int64)
+        fn = self.lib.fphip_hh_get_transform
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        self._chk(fn(self.h, first, count, u.ctypes.data_as(ctypes.c_void_p)), "get_transform")
+        return u
+
+    def get_inverse_transform_t(self, first=0, count=None):
+        """The inverse transpose of the u the device tracks — an integer matrix, u being unimodular.  It is the
+        reference's u_inv_t (MatHouseholder(b, u, u_inv, ...) with enable_inverse_transform, householder.cpp:456-559:
+        every row operation b_i += x b_j is mirrored as u_inv_t_j -= x u_inv_t_i) ONLY for a u that started at the
+        identity.  DERIVED ON THE HOST (exact integer elimination, `gso.inverse_transpose`); the device keeps no
+        u_inv_t of its own.  [count][d][d] Python-int object arrays (entries may leave int64)."""
+        from .gso import inverse_transpose
+        u = self.get_transform(first, count)
+        return np.stack([inverse_transpose(m) for m in u])
+
     def update_R(self, blocked=False):
         """refresh_R_bf() + update_R() for every lattice.  blocked=True: the opt-in MFMA compact-WY
         mode (same R to rounding — 1e-9 on mu / r —, not bit for bit)."""

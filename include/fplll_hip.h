@@ -24,6 +24,7 @@
  *   fphip_hh_*            ← MatHouseholder<Z_NR<long>,FP_NR<double>>   householder.h:70
  *       fphip_hh_update_R       ← refresh_R_bf + update_R               householder.cpp:27-245
  *       fphip_hh_hlll           ← HLLLReduction::hlll                   hlll.cpp:26-499
+ *       fphip_hh_enable_transform ← MatHouseholder(b, u, ...): u follows b  householder.cpp:372-398, 456-559
  *
  * Error convention: 0 = FPHIP_OK; FPHIP_UNSUPPORTED = instance declined, the caller must fall
  * back exactly as fplll does for a plugin returning ~uint64_t(0) (enum/enumerate_ext.cpp:88,
@@ -538,6 +539,19 @@ int fphip_hh_create(fphip_ctx *ctx, int batch, int d, int n, int row_expo, fphip
 void fphip_hh_destroy(fphip_hh *h);
 int fphip_hh_set_basis(fphip_hh *h, int first_lattice, int count, const int64_t *b);
 int fphip_hh_broadcast_basis(fphip_hh *h, int src);
+/* MatHouseholder(b, u, u_inv, flags) with a non-empty u (householder.h:70-130; hlll_reduction(b, u, ...)): the
+ * transformation matrix lives on the device and follows b.  u is [batch][d][d] row-major, NULL = the identity.  After
+ * the call every entry point that changes b applies the same row operation to u — row_addmul_we (householder.cpp:
+ * 522-559) and swap (:372-398), the only two ways hlll.cpp touches b —: fphip_hh_hlll, fphip_hh_hlll_ex at 53, 106 and
+ * 212 bits, fphip_hh_hlll_ladder (its stages continue on the device's b and u) and fphip_hh_size_reduce; so
+ * u_out = T u_in where b_out = T b_in, whatever the status of the lattice (a row of u is written where the row of b
+ * is).  fphip_hh_update_R / _blocked do not touch b; fphip_hh_set_basis keeps u; fphip_hh_broadcast_basis copies
+ * src's u with its b; a second call resets u.  Entries are int64 with wrap-around, like Z_NR<long>.  An object with
+ * d > n is declined (FPHIP_UNSUPPORTED); fphip_hh_get_transform without a tracked u is FPHIP_ERROR.  An object that
+ * never enables it launches the kernels it always did.  u_inv is not kept on the device (the Python layer derives
+ * it from u on the host). */
+int fphip_hh_enable_transform(fphip_hh *h, const int64_t *u);
+int fphip_hh_get_transform(fphip_hh *h, int first, int count, int64_t *u);
 int fphip_hh_update_R(fphip_hh *h, int *status);
 /* The same R-factor in BLOCKED compact-WY form on the MFMA matrix cores (v_mfma_f64_16x16x4_f64):
  * panels of 16 rows, R_panel -= ((R_panel V^T) T) V per block of 16 earlier reflectors.  OPT-IN
