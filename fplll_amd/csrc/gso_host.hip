@@ -106,6 +106,7 @@ struct LllX
   int *slot_out;
 };
 template <int NQ, class FT> __global__ void lll_x_kernel(LllX A);
+template <int NQ, class FT> __global__ void lll_x_u_kernel(LllX A, long long *Uall, long long *U2all, int ldu);
 __global__ void dd_op_kernel(const double *ahi, const double *alo, const double *bhi, const double *blo,
                              double *ohi, double *olo, int op, int count);
 template <class FT> __global__ void ftx_op_kernel(const double *pa, const double *pb, double *po, int op, int count);
@@ -402,7 +403,7 @@ static int transform_guard(fphip_gso *g, const char *what)
   if (!g->P.u)
     return FPHIP_OK;
   snprintf(fphip_ctx_errbuf(g->ctx), 512, "%s: the transformation matrix u is tracked (fphip_gso_enable_transform) and "
-           "this entry point does not update it; fphip_gso_lll / fphip_gso_lll_flags do", what);
+           "this entry point does not update it; fphip_gso_lll / _lll_flags / _lll_ex / _lll_ladder do", what);
   return FPHIP_UNSUPPORTED;
 }
 
@@ -998,6 +999,17 @@ extern "C" int fphip_gso_session_read(fphip_gso *g, int lattice, int64_t *b, dou
 // LLLReduction::lll in a selectable floating-point type (lll_x.hip): precision 106 = double-double on
 // the device (the stand-in for FP_NR<dd_real>: Wrapper::lll's fast_lll<dd_real>, wrapper.cpp:322-330),
 // 53 = plain double with the same (per-lane) summation order.  Same statuses / info as fphip_gso_lll.
+// With a transformation matrix on the device (fphip_gso_enable_transform) the launch is lll_x_u_kernel (lll_x_u.hip):
+// u takes every row operation b takes and leaves in position order through u2, like b through b2.
+//
+// Quad-double with more than one column per lane has never been launched in any form (and the wide quad-double
+// instantiations of the sibling HLLL kernel faulted with the cause still open): with a tracked u
+// that territory is not extended — lll_x_u_kernel<NQ >= 2, QD> does not exist.
+static bool lll_x_u_covers_quad_double(const fphip_gso *g)
+{
+  return !g->P.u || (g->P.d <= 64 && g->P.n <= 64);
+}
+
 static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_end, double delta, double eta,
                       int precision, const int *d_only_failed, int *status, int *info)
 {
@@ -1010,11 +1022,23 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
     snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_gso_lll_ex: need 0 <= kappa_min <= kappa_start < kappa_end <= d <= 256");
     return FPHIP_ERROR;
   }
+  if (precision == 212 && !lll_x_u_covers_quad_double(g))
+  {  // before anything is allocated or launched: b and u stay as they are
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_gso_lll_ex: the transformation matrix u is tracked and quad-double "
+             "(precision 212) carries it for max(d, n) <= 64 only (d = %d, n = %d): the wider quad-double kernels have "
+             "never been launched; precision 106 carries u at every width", g->P.d, g->P.n);
+    return FPHIP_UNSUPPORTED;
+  }
   int rc = ensure_lll_buffers(g);
   if (rc != FPHIP_OK)
     return rc;
   const size_t B = (size_t)g->P.batch, d = g->P.d, ldd = g->P.ldd, ldn = g->P.ldn;
   hipStream_t s = fphip_ctx_stream(g->ctx);
+  if (g->P.u && !g->P.u2)
+  {  // (fphip_gso_enable_transform allocates the pair; an object that lost the second buffer gets it back)
+    GCHK(fphip_dev_alloc((void **)&g->P.u2, B * d * ldd * sizeof(long long) + 4096, s));
+    GCHK(hipMemsetAsync(g->P.u2, 0, B * d * ldd * sizeof(long long) + 4096, s));
+  }
   const size_t n_bf = B * d * ldn, n_pl = B * d * ldd;
   // (bf, then the low planes of mu / r / gf, then — quad-double — two more planes of each)
   const int planes = precision == 212 ? 9 : 3;
@@ -1071,13 +1095,38 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
   A.slot_out = g->x_keep ? (int *)(g->xkeep + 2 * n_pl) : nullptr;
   if (d_only_failed)  // the lattices that are skipped keep their rows: b2 := b first
     GCHK(hipMemcpyAsync(g->P.b2, g->P.b, B * d * ldn * sizeof(long long), hipMemcpyDeviceToDevice, s));
+  if (d_only_failed && g->P.u)  // ... and their rows of u: u2 := u
+    GCHK(hipMemcpyAsync(g->P.u2, g->P.u, B * d * ldd * sizeof(long long), hipMemcpyDeviceToDevice, s));
   const int need = (g->P.d > g->P.n ? g->P.d : g->P.n);
   const int nq   = (need + 63) / 64;
   int grid       = g->P.batch;
   if (grid > fphip_ctx_num_cus(g->ctx) * 8)
     grid = fphip_ctx_num_cus(g->ctx) * 8;
   GCHK(hipEventRecord(g->ev[0], s));
-  if (precision == 212)
+  if (g->P.u)
+  {
+    long long *u = g->P.u, *u2 = g->P.u2;
+    const int ldu = g->P.ldd;
+    if (precision == 212)  // (nq == 1: lll_x_u_covers_quad_double above)
+      hipLaunchKernelGGL((lll_x_u_kernel<1, QD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu);
+    else if (precision == 106)
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL((lll_x_u_kernel<1, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      case 2: hipLaunchKernelGGL((lll_x_u_kernel<2, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      case 3: hipLaunchKernelGGL((lll_x_u_kernel<3, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      default: hipLaunchKernelGGL((lll_x_u_kernel<4, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      }
+    else
+      switch (nq)
+      {
+      case 1: hipLaunchKernelGGL((lll_x_u_kernel<1, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      case 2: hipLaunchKernelGGL((lll_x_u_kernel<2, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      case 3: hipLaunchKernelGGL((lll_x_u_kernel<3, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      default: hipLaunchKernelGGL((lll_x_u_kernel<4, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
+      }
+  }
+  else if (precision == 212)
     switch (nq)
     {
     case 1: hipLaunchKernelGGL((lll_x_kernel<1, QD>), dim3(grid), dim3(64), 0, s, A); break;
@@ -1107,6 +1156,8 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
   float ms = 0;
   GCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
   std::swap(g->P.b, g->P.b2);  // the kernel wrote the rows in position order into b2
+  if (g->P.u)
+    std::swap(g->P.u, g->P.u2);  // ... and those of u into u2 (every launch, whatever its statuses)
   if (g->x_keep)
   {
     GCHK(hipMemcpyAsync(g->xkeep, g->P.mu, n_pl * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -1176,9 +1227,9 @@ extern "C" int fphip_gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, in
                                 double eta, int precision, int *status, int *info)
 {
   FPHIP_RANGE("fphip_gso_lll_ex");
-  if (g)
-    if (int rct = transform_guard(g, "lll_ex"))
-      return rct;
+  if (g && g->P.u)  // (a tracked u used to be refused here; a session keeps its rows in the kernel's slots)
+    if (int rcg = session_guard(g, "fphip_gso_lll_ex"))
+      return rcg;
   return gso_lll_ex(g, kappa_min, kappa_start, kappa_end, delta, eta, precision, nullptr, status, info);
 }
 
@@ -1194,8 +1245,6 @@ extern "C" int fphip_gso_lll_ladder(fphip_gso *g, int kappa_min, int kappa_start
   FPHIP_RANGE("fphip_gso_lll_ladder");
   if (!g)
     return FPHIP_ERROR;
-  if (int rct = transform_guard(g, "lll_ladder"))
-    return rct;
   const size_t B = (size_t)g->P.batch;
   std::vector<int> st(B, 0), inf(4 * B, 0), stg(B, 53);
   int rc = fphip_gso_lll(g, kappa_min, kappa_start, kappa_end, delta, eta, st.data(), inf.data());
@@ -1237,7 +1286,10 @@ extern "C" int fphip_gso_lll_ladder(fphip_gso *g, int kappa_min, int kappa_start
       }
     // third stage (Wrapper::lll goes on to fast_lll<qd_real>, wrapper.cpp:331-339): quad-double for the lattices
     // double-double gave up on (FPHIP_LLL_LADDER_TEST=2, tests only: every fourth lattice as if it had)
-    if (getenv("FPHIP_LLL_LADDER_TEST") && atoi(getenv("FPHIP_LLL_LADDER_TEST")) == 2)
+    // With a tracked u and more than 64 rows or columns there is no third stage (lll_x_u_covers_quad_double): the
+    // lattices double-double gave up on keep their status and stage 106.
+    const bool qd = lll_x_u_covers_quad_double(g);
+    if (qd && getenv("FPHIP_LLL_LADDER_TEST") && atoi(getenv("FPHIP_LLL_LADDER_TEST")) == 2)
       for (size_t L = 3; L < B; L += 4)
         if (!mask[L] && st[L] == 1)
           st[L] = -1;
@@ -1245,7 +1297,7 @@ extern "C" int fphip_gso_lll_ladder(fphip_gso *g, int kappa_min, int kappa_start
     bool any3 = false;
     for (size_t L = 0; L < B; ++L)
     {
-      const bool failed = !mask[L] && (st[L] == 0 || st[L] == -1 || st[L] == -3);
+      const bool failed = qd && !mask[L] && (st[L] == 0 || st[L] == -1 || st[L] == -3);
       mask3[L]          = failed ? 0 : 1;
       any3 |= failed;
     }

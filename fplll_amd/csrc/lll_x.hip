@@ -22,8 +22,24 @@
 // maps positions to physical rows (b, bf, mu, r, row_expo, valid-column counts are keyed by slot; the
 // columns of mu / r are positions — a move invalidates every row from its lower end on, exactly the
 // reference's invalidate_gso_row); the Gram cache is keyed by the pair of slots.
+//
+// FPHIP_LLL_X_U (lll_x_u.hip): the same text compiled as lll_x_u_kernel<NQ, FT>, which carries the transformation
+// matrix u (fphip_gso_enable_transform; [batch][d][ldu] int64, rows keyed by SLOT like b's, lane = column): babai's
+// integer AXPY runs on the row of u next to the row of b — loaded, updated and stored together, so a multiplier beyond
+// 63 bits (status -2) leaves both unwritten and u describes the b on the device whatever the status — and the rows
+// leave in position order into u2 where b's leave into b2.  move_row and the zero rows act on the slot table alone.
+// Without the macro every line of it is compiled out: lll_x_kernel<NQ, FT> is the output of this translation unit as
+// before.
 #include "ftx.h"
 #include "gso_device.h"
+
+#ifdef FPHIP_LLL_X_U
+#define FPHIP_LLL_X_KERNEL lll_x_u_kernel
+#define FPHIP_LLL_X_UARGS , long long *Uall, long long *U2all, int ldu
+#else
+#define FPHIP_LLL_X_KERNEL lll_x_kernel
+#define FPHIP_LLL_X_UARGS
+#endif
 
 namespace fphip
 {
@@ -77,7 +93,7 @@ template <> struct PlaneX<QD>
 
 // status: 1 RED_SUCCESS, 0 RED_GSO_FAILURE, -1 RED_BABAI_FAILURE, -2 multiplier beyond 63 bits,
 // -3 RED_LLL_FAILURE (iteration limit)
-template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(LllX A)
+template <int NQ, class FT> __global__ void __launch_bounds__(64) FPHIP_LLL_X_KERNEL(LllX A FPHIP_LLL_X_UARGS)
 {
   __shared__ int slot[256], vcol[256];
   __shared__ double lov_hi[257], lov_lo[257], rd_hi[256], rd_lo[256];
@@ -92,6 +108,9 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
       continue;
     long long *b = A.b + (size_t)L * dT * ldn;
     double *bf   = A.bf + (size_t)L * dT * ldn;
+#ifdef FPHIP_LLL_X_U
+    long long *u = Uall + (size_t)L * dT * ldu;
+#endif
     const size_t po = (size_t)L * dT * ldd, pp = (size_t)A.batch * dT * ldd;
     const PlaneX<FT> mu{A.mu_hi + po, A.mu_lo ? A.mu_lo + po : nullptr, A.mu_x ? A.mu_x + po : nullptr, A.mu_x ? A.mu_x + pp + po : nullptr};
     const PlaneX<FT> r{A.r_hi + po, A.r_lo ? A.r_lo + po : nullptr, A.r_x ? A.r_x + po : nullptr, A.r_x ? A.r_x + pp + po : nullptr};
@@ -383,6 +402,15 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
           const int c = lane + 64 * q;
           bk[q]       = (c < n) ? b[(size_t)sk * ldn + c] : 0;
         }
+#ifdef FPHIP_LLL_X_U
+        long long uk[NQ];  // the row of u in the same slot: d entries, NQ * 64 >= d
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+        {
+          const int c = lane + 64 * q;
+          uk[q]       = (c < dT) ? u[(size_t)sk * ldu + c] : 0;
+        }
+#endif
         int fail = 0;
         for (int j = kp - 1; j >= 0; --j)
         {
@@ -425,6 +453,16 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
               bk[q] = (long long)((unsigned long long)bk[q] +
                                   (unsigned long long)b[(size_t)sj * ldn + c] * (unsigned long long)lx);
           }
+#ifdef FPHIP_LLL_X_U
+#pragma unroll
+          for (int q = 0; q < NQ; ++q)
+          {  // u[kappa] += lx u[j], gso.cpp:246-247 (Z_NR<long>: wraps)
+            const int c = lane + 64 * q;
+            if (c < dT)
+              uk[q] = (long long)((unsigned long long)uk[q] +
+                                  (unsigned long long)u[(size_t)sj * ldu + c] * (unsigned long long)lx);
+          }
+#endif
         }
         if (fail)
           return fail;
@@ -435,6 +473,15 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
           if (c < n)
             b[(size_t)sk * ldn + c] = bk[q];
         }
+#ifdef FPHIP_LLL_X_U
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+        {  // (lane c alone reads and writes column c of u: no fence is owed to another lane)
+          const int c = lane + 64 * q;
+          if (c < dT)
+            u[(size_t)sk * ldu + c] = uk[q];
+        }
+#endif
         __threadfence_block();
         row_op_end(kp);
       }
@@ -637,6 +684,20 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
           out[(size_t)p * ldn + c] = (c < n) ? b[(size_t)s * ldn + c] : 0;
       }
     }
+#ifdef FPHIP_LLL_X_U
+    long long *uout = U2all + (size_t)L * dT * ldu;
+    for (int p = 0; p < dT; ++p)
+    {
+      const int s = slot[p];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+      {
+        const int c = lane + 64 * q;
+        if (c < ldu)
+          uout[(size_t)p * ldu + c] = (c < dT) ? u[(size_t)s * ldu + c] : 0;
+      }
+    }
+#endif
     if (A.slot_out)
       for (int p = lane; p < dT; p += 64)
         A.slot_out[(size_t)L * dT + p] = slot[p];
@@ -652,6 +713,20 @@ template <int NQ, class FT> __global__ void __launch_bounds__(64) lll_x_kernel(L
   }
 }
 
+#ifdef FPHIP_LLL_X_U
+// (quad-double with more than one column per lane has never been launched in any form, and the sibling
+// hlll_x_kernel<NQ >= 2, QD> faulted with the cause still open, DESIGN.md section 4d: the host refuses it with a
+// tracked u, so there is nothing to instantiate)
+template __global__ void lll_x_u_kernel<1, double>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<2, double>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<3, double>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<4, double>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<1, DD>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<2, DD>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<3, DD>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<4, DD>(LllX, long long *, long long *, int);
+template __global__ void lll_x_u_kernel<1, QD>(LllX, long long *, long long *, int);
+#else
 template __global__ void lll_x_kernel<1, double>(LllX);
 template __global__ void lll_x_kernel<2, double>(LllX);
 template __global__ void lll_x_kernel<3, double>(LllX);
@@ -664,5 +739,6 @@ template __global__ void lll_x_kernel<1, QD>(LllX);
 template __global__ void lll_x_kernel<2, QD>(LllX);
 template __global__ void lll_x_kernel<3, QD>(LllX);
 template __global__ void lll_x_kernel<4, QD>(LllX);
+#endif  // FPHIP_LLL_X_U
 
 }  // namespace fphip

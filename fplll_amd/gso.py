@@ -135,8 +135,11 @@ class MatGSOBatch:
     def enable_transform(self, u=None):
         """MatGSO(b, u, ...) with a non-empty u (enable_transform): track the transformation matrix on the device —
         u [batch][d][d] int64, or None for the identity.  lll() then applies every row operation to u as well
-        (gso.cpp:84-158), and so do bkz() / bkz_strategies() with transform=True; the entry points that do not
-        raise Unsupported while it is tracked."""
+        (gso.cpp:84-158); u is carried by lll_ex() at 53, 106 and 212 bits and by every stage of lll_ladder() too
+        (get_transform() = T u_in with b_out = T b_in, also after a failing status), and by bkz() / bkz_strategies()
+        with transform=True.  One limit: quad-double (lll_ex(212), the ladder's third stage) carries u for
+        max(d, n) <= 64 only.  The entry points that do not update u (size_reduction, bkz* without transform=True,
+        slide_pass) raise Unsupported while it is tracked."""
         fn = self.lib.fphip_gso_enable_transform
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -238,8 +241,11 @@ class MatGSOBatch:
 
     def lll_ex(self, precision=106, kappa_min=0, kappa_start=0, kappa_end=-1, delta=LLL_DEF_DELTA,
                eta=LLL_DEF_ETA):
-        """LLLReduction::lll in double-double (precision 106) or plain double (53) — lll_x.hip; the
-        second stage of the LLL-side precision ladder.  Returns (status[batch], info[batch][4])."""
+        """LLLReduction::lll in double-double (precision 106), quad-double (212) or plain double (53) — lll_x.hip;
+        the later stages of the LLL-side precision ladder.  Returns (status[batch], info[batch][4]).
+        After enable_transform() the transformation matrix u is carried (lll_x_u.hip): every row operation on b is
+        applied to u, whatever the status; status, info and basis are those of the run without u.  Quad-double
+        carries u for max(d, n) <= 64 only: beyond, precision 212 raises Unsupported and leaves b and u alone."""
         st = np.zeros(self.batch, dtype=np.int32)
         info = np.zeros((self.batch, 4), dtype=np.int32)
         fn = self.lib.fphip_gso_lll_ex
@@ -273,7 +279,10 @@ class MatGSOBatch:
 
     def lll_ladder(self, kappa_min=0, kappa_start=0, kappa_end=-1, delta=LLL_DEF_DELTA, eta=LLL_DEF_ETA):
         """Wrapper::lll's precision ladder on the device (wrapper.cpp:281-359): the exact double kernel,
-        then double-double for the lattices that fail in double.  Returns (status, info, stage)."""
+        then double-double for the lattices that fail in double, then quad-double.  Returns (status, info, stage).
+        After enable_transform() the transformation matrix u is carried through every stage: each one continues on
+        the b and the u the stage before left on the device.  With u tracked and max(d, n) > 64 there is no
+        quad-double stage: a lattice double-double gives up on keeps its status and stage 106."""
         st = np.zeros(self.batch, dtype=np.int32)
         info = np.zeros((self.batch, 4), dtype=np.int32)
         stage = np.zeros(self.batch, dtype=np.int32)
@@ -728,6 +737,53 @@ def bkz_reduction(ctx, b, block_size, strategies=None, rnd=None, with_u=True, de
     if single:
         return b_out[0], (None if u is None else u[0]), int(status[0]), info[0]
     return b_out, u, status, info
+
+
+LLL_METHODS = ("wrapper", "fast")
+LLL_FLOAT_TYPES = {"double": 53, "dd": 106, "qd": 212}  # method="fast": the precision of lll() / lll_ex()
+
+
+def lll_reduction(ctx, b, with_u=True, delta=LLL_DEF_DELTA, eta=LLL_DEF_ETA, method="wrapper", float_type="double"):
+    """lll_reduction(b, u, delta, eta, method, float_type) (lll_reduction_z, wrapper.cpp:576-734) for the cases the device covers:
+      method="fast", float_type="double"   LLLReduction<Z_NR<long>, FP_NR<double>>: MatGSOBatch.lll()
+      method="fast", float_type="dd"       ... <dd_real>: lll_ex(106)
+      method="fast", float_type="qd"       ... <qd_real>: lll_ex(212)
+      method="wrapper"                     Wrapper::lll's ladder of the fast types: lll_ladder() (float_type "double")
+    Anything else (proved / heuristic, long double, dpe, mpfr, a float type with the wrapper) is a ValueError before
+    any device call.  b: one basis [d][n] or a batch [batch][d][n]; with_u=False skips the tracking.
+    Returns (b_out, u, status, stage) — u None without with_u; u b = b_out in exact integers, whatever the status;
+    stage: the precision each lattice ended at (53, 106 or 212); for one basis the leading batch axis is dropped."""
+    if method not in LLL_METHODS:
+        raise ValueError("lll_reduction: method %r is not covered on the device (%s)" % (method, ", ".join(LLL_METHODS)))
+    if method == "wrapper" and float_type != "double":
+        raise ValueError("lll_reduction: the wrapper chooses its own float types (float_type=%r)" % (float_type,))
+    if float_type not in LLL_FLOAT_TYPES:
+        raise ValueError("lll_reduction: float_type %r is not covered on the device (%s)"
+                         % (float_type, ", ".join(LLL_FLOAT_TYPES)))
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    if b.ndim not in (2, 3):
+        raise ValueError("lll_reduction: b is [d][n] or [batch][d][n]")
+    single = b.ndim == 2
+    if single:
+        b = b[None]
+    g = MatGSOBatch(ctx, b.shape[0], b.shape[1], b.shape[2])
+    try:
+        g.set_basis(b)
+        if with_u:
+            g.enable_transform()
+        precision = LLL_FLOAT_TYPES[float_type]
+        if method == "wrapper":
+            status, _, stage = g.lll_ladder(delta=delta, eta=eta)
+        else:
+            status, _ = g.lll(delta=delta, eta=eta) if precision == 53 else g.lll_ex(precision, delta=delta, eta=eta)
+            stage = np.full(b.shape[0], precision, dtype=np.int32)
+        b_out = g.get_basis()
+        u = g.get_transform() if with_u else None
+    finally:
+        g.close()
+    if single:
+        return b_out[0], (None if u is None else u[0]), int(status[0]), int(stage[0])
+    return b_out, u, status, stage
 
 
 class BKZAutoAbort:

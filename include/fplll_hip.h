@@ -241,11 +241,16 @@ int fphip_gso_lll_flags(fphip_gso *g, int kappa_min, int kappa_start, int kappa_
 /* MatGSO(b, u, u_inv_t, flags) with a non-empty u (enable_transform, gso_interface.h:96-110): the transformation
  * matrix goes to the device — u [batch][d][d] row-major, or NULL for the identity — and fphip_gso_lll /
  * fphip_gso_lll_flags apply every row operation to its rows as well and move them with b's (gso.cpp:84-158,
- * 289-366): afterwards u_out = T u_in with b_out = T b_in.  Sessions (below) keep u too: a dirty row is then its n
+ * 289-366): afterwards u_out = T u_in with b_out = T b_in.  fphip_gso_lll_ex (precision 53, 106 and 212) and every
+ * stage of fphip_gso_lll_ladder carry u in the same way, in kernels of their own (lll_x_u_kernel): u_out = T u_in
+ * with b_out = T b_in, also after a failing status (a row of u is written where the row of b is; entries are int64
+ * with wrap-around, like Z_NR<long>).  One limit: quad-double (precision 212) carries u for max(d, n) <= 64 only —
+ * beyond, fphip_gso_lll_ex returns FPHIP_UNSUPPORTED with a fphip_last_error text before anything is launched (b and
+ * u untouched), and fphip_gso_lll_ladder has no third stage: the lattices double-double gave up on keep their status
+ * and stage 106.  Sessions (below) keep u too: a dirty row is then its n
  * integers of b followed by its d integers of u, fphip_gso_session_read_transform returns u in position order.
- * While u is tracked the entry points that do not update it (size_reduce, bkz* without FPHIP_BKZ_TRANSFORM, slide,
- * lll_ex / ladder) return FPHIP_UNSUPPORTED; fphip_gso_set_basis keeps u.  u_inv_t (enable_inverse_transform) is
- * not offered. */
+ * While u is tracked the entry points that do not update it (size_reduce, bkz* without FPHIP_BKZ_TRANSFORM, slide)
+ * return FPHIP_UNSUPPORTED; fphip_gso_set_basis keeps u.  u_inv_t (enable_inverse_transform) is not offered. */
 int fphip_gso_enable_transform(fphip_gso *g, const int64_t *u);
 int fphip_gso_get_transform(fphip_gso *g, int first, int count, int64_t *u);
 /* The same lll() on a RESIDENT MatGSO: fplll's MatGSO is an object whose rows, Gram cache, mu / r and
@@ -429,7 +434,8 @@ int fphip_gso_slide_reduction_blocks(fphip_gso **gs, int count, int block_size, 
  * runs, wrapper.cpp:322-330; libqd's algorithms restated, csrc/ftx.h), 53 = plain double.  Same
  * algorithm (lll.cpp:44-224), statuses and info as fphip_gso_lll; sums are accumulated per lane, not in
  * the reference's order, so results are the reference's up to rounding (at 106 bits the decisions carry
- * ~50 bits of slack).  d <= 256. */
+ * ~50 bits of slack).  d <= 256.  A transformation matrix on the device is carried
+ * (fphip_gso_enable_transform, above; precision 212 with it: max(d, n) <= 64). */
 int fphip_gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_end, double delta, double eta,
                      int precision, int *status, int *info);
 /* The LLL-side precision ladder of the reference's wrapper (Wrapper::lll, wrapper.cpp:281-359: double
@@ -438,7 +444,8 @@ int fphip_gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_end
  * stopped with RED_GSO_FAILURE (0), RED_BABAI_FAILURE (-1) or RED_LLL_FAILURE (-3) — BASELINE config
  * 5's 256-dim NTRU-like lattice is such a case ("infinite loop in babai" in double, in the reference
  * and here).  stage[batch] (nullable): 53 or 106.  A lattice that fails at 106 bits too keeps its
- * status — the caller's MPFR stage is next. */
+ * status — the caller's MPFR stage is next.  A transformation matrix on the device is carried through
+ * every stage (fphip_gso_enable_transform, above). */
 int fphip_gso_lll_ladder(fphip_gso *g, int kappa_min, int kappa_start, int kappa_end, double delta, double eta,
                          int *status, int *info, int *stage);
 
