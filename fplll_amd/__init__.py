@@ -8,3 +8,4 @@ from ._lib import Context, HipError, load, LIB_PATH  # noqa: F401
 from .enumeration import (  # noqa: F401
     EVALSTRATEGY_BEST_N_SOLUTIONS, EVALSTRATEGY_FIRST_N_SOLUTIONS,
     EVALSTRATEGY_OPPORTUNISTIC_N_SOLUTIONS, FastEvaluator, Unsupported, enumerate_block)
+from .cvp import closest_vector, closest_vectors  # noqa: F401

@@ -66,6 +66,10 @@ template <bool DUAL>
 __global__ void enum_bfs_cvp_kernel(DevShared *g, double maxdist, QueueMem *qm, TaskBuf f0, TaskBuf f1, TaskBuf fin, int L0,
                                     int nlev, int floor_level, float heavy, int count_nodes, int compact_n, int shard_index,
                                     int shard_count);
+template <int NQT, bool SUBS, bool DUAL>
+__global__ void enum_top_cvp_kernel(DevShared *g, HostCtl *h, TopBuf in, unsigned n_in, TopBuf out_top, int stop,
+                                    TaskBuf out, double *xhi_root, int d, double maxdist, int count_nodes, int launch_idx,
+                                    double *gtop);
 // enum_deal.hip: the content-sorted snake deal of a multi-rank call on the device
 size_t deal_work_bytes(unsigned n);
 unsigned deal_tasks_device(hipStream_t s, const unsigned long long *keys, const double *pd, const unsigned *slot_of,
@@ -176,6 +180,7 @@ struct fphip_ctx
   void *order_work             = nullptr;  // device: scratch of the depth-first ordering of the tasks (enum_order.hip)
   size_t order_work_bytes      = 0;
   int ordered_running          = 0;        // an ordered call is in flight: fphip_enum_lower_bound is ignored
+  int cvp_wide                 = 0;        // closest-vector calls above 64 rows are taken (fphip_ctx_allow_wide_target)
   double *xhi_root             = nullptr;  // device: cap * 64 doubles: the coefficients of levels >= 64 per level-64
                                            // ancestor (blocks larger than 64; 64 doubles per started chunk of levels)
   QueueMem *qm                 = nullptr;  // device: ticket / emission counters of the current call
@@ -419,6 +424,18 @@ int fphip_ctx_device(fphip_ctx *ctx) { return ctx->device; }
 // the worker thread that answers its mailbox — a multi-gigabyte allocation there would stall the kernel at best)
 // a context whose enumerations are known to be small (the extra hand-off contexts of a batch of tours: blocks of at
 // most 64 rows) can hold its three task generations in a fraction of the default 3.6 GB; before the first run only
+// Closest-vector calls (fphip_enum_opts::target) on blocks of 65 .. 256 rows are OPT-IN: by default they are declined
+// with the text they always had; FPHIP_CVP_WIDE=1 in the environment takes them, and so does this switch, which the
+// closest-vector solver (fphip_closest_vector, gso_host.hip) sets around its own enumerations.  Returns the old value.
+int fphip_ctx_allow_wide_target(fphip_ctx *ctx, int on)
+{
+  if (!ctx)
+    return 0;
+  const int old = ctx->cvp_wide;
+  ctx->cvp_wide = on ? 1 : 0;
+  return old;
+}
+
 int fphip_ctx_set_task_cap(fphip_ctx *ctx, unsigned cap)
 {
   if (!ctx || ctx->qm || cap < 4096)
@@ -820,7 +837,11 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
     o.exchange_chunks = 1;
   const int d = dim;
   if (d < 2 || d > FPHIP_ENUM_MAX_DIM || (o.findsubsols && !subcb))
+  {
+    if (d > FPHIP_ENUM_MAX_DIM)
+      snprintf(ctx->err, sizeof ctx->err, "enumeration: more than %d rows", FPHIP_ENUM_MAX_DIM);
     return FPHIP_UNSUPPORTED;  // → ~uint64_t(0): fplll falls back (enumerate_ext.cpp:88)
+  }
   // dual enumeration (enumerate_base.cpp:57-61, 103-105; the caller passes the transformed mu / r of
   // enumerate.cpp:107-123): without sub-solutions, as the reference's dual caller has it
   // (BKZReduction's evaluator is built with find_subsolutions = false, bkz.cpp:327-331)
@@ -832,7 +853,8 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
   const bool ordered = o.ordered != 0;
   // (a bound exchange between ranks is declined with them: the bound it would publish is a foreign one, the same
   //  hazard fphip_enum_lower_bound is ignored for)
-  if (ordered && (dual || subs || d > 64 || o.shard_count > 1 || o.exchange))
+  // (a target is declined by its own check below, with its own text)
+  if (ordered && !o.target && (dual || subs || d > 64 || o.shard_count > 1 || o.exchange))
   {
     snprintf(ctx->err, sizeof ctx->err,
              "ordered enumeration: not with dual, findsubsols, more than 64 rows, several ranks or a bound exchange");
@@ -845,7 +867,8 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
     const char *with = dual                                        ? "dual (the reference refuses the pair as well)"
                        : subs                                      ? "findsubsols"
                        : ordered                                   ? "ordered (reference-order mode)"
-                       : d > 64                                    ? "more than 64 rows"
+                       : (d > 64 && !ctx->cvp_wide && env_int("FPHIP_CVP_WIDE", 0) == 0)
+                           ? "more than 64 rows (opt-in: FPHIP_CVP_WIDE=1)"
                        : (o.shard_count > 1 || o.exchange || o.gather) ? "several ranks (shard_count, exchange, gather)"
                                                                    : nullptr;
     if (with)
@@ -927,7 +950,8 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
   }
   // closest-vector mode: the root task's column is the target (center_partsum[i] = target_coord[i],
   // enumerate.cpp:85-89), rows >= d zero; every centre below comes out of it by the walk's S_k = S_{k+1} - x mu_k
-  double root_col[64];
+  // (blocks above 64 rows: the root TOP task's column, all d rows of it)
+  double root_col[FPHIP_ENUM_MAX_DIM];
   memset(root_col, 0, sizeof root_col);
   if (cvp)
     memcpy(root_col, o.target, (size_t)d * sizeof(double));
@@ -990,7 +1014,7 @@ restart:
   // stage reads its first frontier from buf[1] and leaves the final task list in buf[0])
   int cur = use_bfs ? 1 : 0;
   if (cvp)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->buf[cur].col, root_col, sizeof root_col, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->buf[cur].col, root_col, 64 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   else
     HIPCHK(ctx, hipMemsetAsync(ctx->buf[cur].col, 0, 64 * sizeof(double), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->buf[cur].x, 0, 64 * sizeof(double), ctx->stream));
@@ -1018,8 +1042,12 @@ restart:
       HIPCHK(ctx, fphip_dev_alloc((void **)&ctx->top[b].count, 64, ctx->stream));
       ctx->top[b].cap = cap2;
     }
-    // root top task: level d, zero column, no coefficient chosen, zero partial distance
-    HIPCHK(ctx, hipMemsetAsync(ctx->top[0].col, 0, 256 * sizeof(double), ctx->stream));
+    // root top task: level d, zero column (closest-vector mode: the target over all d rows), no coefficient chosen,
+    // zero partial distance
+    if (cvp)
+      HIPCHK(ctx, hipMemcpyAsync(ctx->top[0].col, root_col, 256 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    else
+      HIPCHK(ctx, hipMemsetAsync(ctx->top[0].col, 0, 256 * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->top[0].xhi, 0, 192 * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->top[0].pd, 0, sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->top[0].level, &d, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -1071,7 +1099,19 @@ restart:
   hipLaunchKernelGGL((enum_top_kernel<N, S_, D_>), dim3(grid), dim3(64), tlds, ctx->stream, ctx->g, ctx->h,          \
                      ctx->top[in_idx], n_in, ctx->top[in_idx ^ 1], stop, top_out, ctx->xhi_root, d, maxdist,        \
                      top_count, launch_idx, ctx->gtop)
-      if (wide)
+      if (cvp)
+      {  // closest-vector mode: the top walk compiled for it (primal, no sub-solutions)
+#define FPHIP_TOP_LAUNCH_CVP(N)                                                                                    \
+  hipLaunchKernelGGL((enum_top_cvp_kernel<N, false, false>), dim3(grid), dim3(64), tlds, ctx->stream, ctx->g, ctx->h, \
+                     ctx->top[in_idx], n_in, ctx->top[in_idx ^ 1], stop, top_out, ctx->xhi_root, d, maxdist,        \
+                     top_count, launch_idx, ctx->gtop)
+        if (wide)
+          FPHIP_TOP_LAUNCH_CVP(4);
+        else
+          FPHIP_TOP_LAUNCH_CVP(2);
+#undef FPHIP_TOP_LAUNCH_CVP
+      }
+      else if (wide)
       {
         if (dual)
           FPHIP_TOP_LAUNCH(4, false, true);
@@ -1776,7 +1816,7 @@ restart:
     // sequence: newcenter -= x[j] * mut[k][j], j ascending; roundto: ties away from zero; the loop tests maxdist, not
     // the pruned bounds).  The reference subtracts in unsigned arithmetic without a check: a level the walk never
     // reached ends at 2^64 - 1 there, and here.
-    double xr[64];
+    double xr[FPHIP_ENUM_MAX_DIM];  // (all d rows: the levels >= 64 of a block above 64 rows are compensated as well)
     double newdist = 0.0;
     int k          = d - 1;
     for (; k >= 0 && newdist <= maxdist; --k)

@@ -54,9 +54,9 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off  (no FMA contraction: fplll's
 // arithmetic is separate multiply and add, nr/nr_FP_d.inl:178, baseline x86-64 build).
 //
-// Closest-vector mode (FPHIP_CVP): enum_kernel_cvp.hip compiles the text of enum_phase_kernel
-// and enum_bfs_kernel a second time with FPHIP_CVP = 1, into kernels of another name (enum_phase_cvp_kernel,
-// enum_bfs_cvp_kernel): the reference's walk with a target (!is_svp) takes the zig-zag at every node, the root
+// Closest-vector mode (FPHIP_CVP): enum_kernel_cvp.hip compiles the text of enum_phase_kernel,
+// enum_bfs_kernel and enum_top_kernel a second time with FPHIP_CVP = 1, into kernels of another name
+// (enum_phase_cvp_kernel, enum_bfs_cvp_kernel, enum_top_cvp_kernel): the reference's walk with a target (!is_svp) takes the zig-zag at every node, the root
 // included (enumerate_base.cpp:80), and hands a leaf at distance exactly 0 to the evaluator (:44 / :99) — the
 // `if constexpr (CVP)` lines below; the target itself sits in the root task's column.  Without the macro the text is
 // what it was: the kernels of the shortest-vector walk keep their names and their code.
@@ -74,7 +74,9 @@
 #if FPHIP_CVP
 #define FPHIP_PHASE_KERNEL enum_phase_cvp_kernel
 #define FPHIP_BFS_KERNEL enum_bfs_cvp_kernel
+#define FPHIP_TOP_KERNEL enum_top_cvp_kernel
 #else
+#define FPHIP_TOP_KERNEL enum_top_kernel
 #define FPHIP_PHASE_KERNEL enum_phase_kernel
 #define FPHIP_BFS_KERNEL enum_bfs_kernel
 #endif
@@ -922,8 +924,10 @@ template __global__ void FPHIP_BFS_KERNEL<false>(DevShared *, double, QueueMem *
 #if !FPHIP_CVP
 template __global__ void enum_bfs_kernel<true>(DevShared *, double, QueueMem *, TaskBuf, TaskBuf, TaskBuf, int, int,
                                                int, float, int, int, int, int);
+#endif
 
-// (the top walk and the task helpers below are compiled once: blocks above 64 rows take no target)
+// (the top walk is compiled for both modes — enum_top_cvp_kernel<NQT, false, false> under the macro —, the task
+//  helpers below it once)
 
 // ---------------------------------------------------------------------------------------------
 // Blocks larger than 64 (up to 256): the levels 64..d-1.  The TOP of the tree is walked with two
@@ -963,11 +967,12 @@ template <int NQT> __device__ __forceinline__ int rlqi(const int (&v)[NQT], int 
 // the levels >= 64 (TopBuf::xhi); xhi_root's rows have the stride every reader computes from d.
 template <int NQT, bool SUBS, bool DUAL>
 __global__ void __launch_bounds__(64)
-    enum_top_kernel(DevShared *__restrict__ g, HostCtl *__restrict__ h, TopBuf in, unsigned n_in,
+    FPHIP_TOP_KERNEL(DevShared *__restrict__ g, HostCtl *__restrict__ h, TopBuf in, unsigned n_in,
                     TopBuf out_top, int stop, TaskBuf out, double *__restrict__ xhi_root, int d,
                     double maxdist, int count_nodes, int launch_idx, double *__restrict__ gtop)
 {
   extern __shared__ __attribute__((aligned(16))) double stk_lds[];  // NQT == 2: slots 65..d (slot k: k doubles)
+  constexpr bool CVP = FPHIP_CVP != 0;  // closest-vector mode: the zig-zag at every node (the root's included)
   constexpr int COLS = 64 * NQT, XS = 64 * (NQT - 1);
   const int lane   = threadIdx.x & 63;
   const int off65  = tri_off(65);
@@ -1172,7 +1177,7 @@ __global__ void __launch_bounds__(64)
         const double ck  = rlq<NQT>(cs, k);
         const double pdk = rlq<NQT>(pds, k);
         int dxk = rlqi<NQT>(dxs, k), ddxk = rlqi<NQT>(ddxs, k);
-        if (pdk != 0.0)
+        if (CVP || pdk != 0.0)
         {
           xk += (double)dxk;
           ddxk = -ddxk;
@@ -1226,15 +1231,21 @@ __global__ void __launch_bounds__(64)
   }
 }
 #define FPHIP_TOP_INST(N, S_, D_)                                                                                  \
-  template __global__ void enum_top_kernel<N, S_, D_>(DevShared *, HostCtl *, TopBuf, unsigned, TopBuf, int, TaskBuf, \
-                                                      double *, int, double, int, int, double *);
+  template __global__ void FPHIP_TOP_KERNEL<N, S_, D_>(DevShared *, HostCtl *, TopBuf, unsigned, TopBuf, int, TaskBuf, \
+                                                       double *, int, double, int, int, double *);
 FPHIP_TOP_INST(2, false, false)
+#if !FPHIP_CVP  // (a target comes without sub-solutions and without dual)
 FPHIP_TOP_INST(2, true, false)
 FPHIP_TOP_INST(2, false, true)
+#endif
 FPHIP_TOP_INST(4, false, false)
+#if !FPHIP_CVP
 FPHIP_TOP_INST(4, true, false)
 FPHIP_TOP_INST(4, false, true)
+#endif
 #undef FPHIP_TOP_INST
+
+#if !FPHIP_CVP
 
 // Work movement between ranks: tasks [lo, lo + n) of a buffer as contiguous records of FPHIP_TASK_REC (+ xstr)
 // doubles — partial distance, root level, column, coefficient prefix and, for a block above 64 rows, the xstr

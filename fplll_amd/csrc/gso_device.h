@@ -177,5 +177,27 @@ struct HhBatch
   double *bf;
   int *info;
 };
+// Batched target preparation of the closest-vector solver (cvp_prepare.hip): one target per lane
+struct CvpPrep
+{
+  int T, ldt;  // number of targets; lanes per workspace row (T rounded up to 64)
+  int d, n, ldn;
+  int max_passes;
+  const long long *b;  // [d][ldn] the lattice's integer basis
+  const double *bfd;   // [d][n]   (double) b(i,j)
+  const double *mu;    // [d][d]   true mu(i,j), j < i
+  const double *rd;    // [d]      true r(i,i)
+  const long long *targets;  // [T][n]
+  long long *coef;           // [T][d]
+  double *tcoord;            // [T][d]
+  double *descent;           // [T]
+  int *status;               // [T]
+  // workspace, one column per lane
+  double *wv;     // [n][ldt] the running target as doubles
+  double *wc;     // [d][ldt] its Gram-Schmidt coordinates
+  double *wx;     // [d][ldt] the nearest-plane vector
+  long long *wt;  // [n][ldt] the running integer target
+  long long *wk;  // [d][ldt] the accumulated coefficients
+};
 }  // namespace fphip
 #endif

@@ -113,6 +113,11 @@ template <class FT> __global__ void ftx_op_kernel(const double *pa, const double
 template <int NQ, bool EARLY>
 __global__ void lll_kernel(GsoBatch P, int kmin, int kstart, int kend, double delta, double eta,
                            double logdelta);
+// cvp_prepare.hip: the closest-vector solver's target preparation and MatGSOInterface::babai, one target per lane
+__global__ void cvp_unscale_kernel(GsoBatch P, int lattice, double *bfd, double *mu, double *rd);
+__global__ void cvp_prepare_kernel(CvpPrep P);
+__global__ void cvp_babai_kernel(int T, int ldt, int d, int start, int dimension, const double *mu, const double *v,
+                                 long long *w, int *status, double *wx);
 }
 using namespace fphip;
 
@@ -122,6 +127,7 @@ int fphip_ctx_num_cus(fphip_ctx *ctx);
 int fphip_ctx_device(fphip_ctx *ctx);
 int fphip_ctx_ensure_task_buffers(fphip_ctx *ctx);  // enum_host.hip
 int fphip_ctx_set_task_cap(fphip_ctx *ctx, unsigned cap);
+int fphip_ctx_allow_wide_target(fphip_ctx *ctx, int on);  // enum_host.hip: closest-vector calls above 64 rows
 
 struct fphip_gso
 {
@@ -3051,6 +3057,289 @@ extern "C" int fphip_gso_get_row_expo(fphip_gso *g, int lattice, int64_t *row_ex
     return rcg;
   GCHK(hipMemcpy(row_expo, g->P.rexp + (size_t)lattice * g->P.d, sizeof(long long) * g->P.d,
                  hipMemcpyDeviceToHost));
+  return FPHIP_OK;
+}
+
+// ---- closest vectors: target preparation, MatGSOInterface::babai, the solver (cvp_prepare.hip) -------------------
+namespace
+{
+// device blocks of one call, back to the cache when it returns
+struct CvpBufs
+{
+  hipStream_t s;
+  std::vector<void *> ptrs;
+  explicit CvpBufs(hipStream_t s_) : s(s_) {}
+  ~CvpBufs()
+  {
+    for (void *p : ptrs)
+      fphip_dev_free(p, s);
+  }
+  template <class T> hipError_t get(T **p, size_t count)
+  {
+    void *q            = nullptr;
+    const hipError_t e = fphip_dev_alloc(&q, (count ? count : 1) * sizeof(T), s);
+    if (e == hipSuccess)
+      ptrs.push_back(q);
+    *p = (T *)q;
+    return e;
+  }
+};
+}  // namespace
+
+static int cvp_lattice_guard(fphip_gso *g, int lattice, int T, const char *what)
+{
+  if (lattice < 0 || lattice >= g->P.batch || T <= 0)
+  {
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "%s: bad lattice index or number of targets", what);
+    return FPHIP_ERROR;
+  }
+  return session_guard(g, what);
+}
+
+// true mu [d][d], true r_ii [d] and the basis as doubles [d][n] of one lattice, on the device
+static int cvp_unscale(fphip_gso *g, int lattice, CvpBufs &B, double **bfd, double **mu, double **rd)
+{
+  const size_t d = g->P.d, n = g->P.n;
+  GCHK(B.get(bfd, d * n));
+  GCHK(B.get(mu, d * d));
+  GCHK(B.get(rd, d));
+  const size_t work = std::max(d * d, d * n);
+  hipLaunchKernelGGL(cvp_unscale_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, B.s, g->P, lattice, *bfd, *mu,
+                     *rd);
+  GCHK(hipGetLastError());
+  return FPHIP_OK;
+}
+
+// the preparation over T targets; mu_h / rd_h (nullable): the true mu [d][d] and r_ii [d] the kernel used
+static int cvp_prepare_run(fphip_gso *g, int lattice, int T, const int64_t *targets, int64_t *coef, double *target_coord,
+                           double *descent, int *status, double *mu_h, double *rd_h)
+{
+  const size_t d = g->P.d, n = g->P.n, ldt = ((size_t)T + 63) / 64 * 64;
+  hipStream_t s = fphip_ctx_stream(g->ctx);
+  CvpBufs B(s);
+  CvpPrep P;
+  memset(&P, 0, sizeof P);
+  double *bfd = nullptr, *mu = nullptr, *rd = nullptr;
+  if (int rc = cvp_unscale(g, lattice, B, &bfd, &mu, &rd))
+    return rc;
+  long long *tg = nullptr;
+  GCHK(B.get(&tg, (size_t)T * n));
+  GCHK(B.get(&P.coef, (size_t)T * d));
+  GCHK(B.get(&P.tcoord, (size_t)T * d));
+  GCHK(B.get(&P.descent, (size_t)T));
+  GCHK(B.get(&P.status, (size_t)T));
+  GCHK(B.get(&P.wv, n * ldt));
+  GCHK(B.get(&P.wc, d * ldt));
+  GCHK(B.get(&P.wx, d * ldt));
+  GCHK(B.get(&P.wt, n * ldt));
+  GCHK(B.get(&P.wk, d * ldt));
+  GCHK(hipMemcpy(tg, targets, (size_t)T * n * sizeof(long long), hipMemcpyHostToDevice));
+  GCHK(hipStreamSynchronize(nullptr));  // (see fphip_gso_set_basis)
+  P.T = T, P.ldt = (int)ldt, P.d = (int)d, P.n = (int)n, P.ldn = g->P.ldn;
+  P.max_passes = 0x100;  // where the reference starts to warn (svpcvp.cpp:573)
+  P.b          = g->P.b + (size_t)lattice * d * g->P.ldn;
+  P.bfd = bfd, P.mu = mu, P.rd = rd, P.targets = tg;
+  GCHK(hipEventRecord(g->ev[0], s));
+  hipLaunchKernelGGL(cvp_prepare_kernel, dim3((unsigned)(ldt / 64)), dim3(64), 0, s, P);
+  GCHK(hipGetLastError());
+  GCHK(hipEventRecord(g->ev[1], s));
+  GCHK(hipStreamSynchronize(s));
+  GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  GCHK(hipMemcpy(coef, P.coef, (size_t)T * d * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(target_coord, P.tcoord, (size_t)T * d * sizeof(double), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(descent, P.descent, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(status, P.status, (size_t)T * sizeof(int), hipMemcpyDeviceToHost));
+  if (mu_h)
+    GCHK(hipMemcpy(mu_h, mu, d * d * sizeof(double), hipMemcpyDeviceToHost));
+  if (rd_h)
+    GCHK(hipMemcpy(rd_h, rd, d * sizeof(double), hipMemcpyDeviceToHost));
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_cvp_prepare(fphip_gso *g, int lattice, int T, const int64_t *targets, int64_t *coef,
+                                 double *target_coord, double *descent, int *status)
+{
+  FPHIP_RANGE("fphip_cvp_prepare");
+  if (!g || !targets || !coef || !target_coord || !descent || !status)
+    return FPHIP_ERROR;
+  if (int rc = cvp_lattice_guard(g, lattice, T, "fphip_cvp_prepare"))
+    return rc;
+  return cvp_prepare_run(g, lattice, T, targets, coef, target_coord, descent, status, nullptr, nullptr);
+}
+
+extern "C" int fphip_gso_babai(fphip_gso *g, int lattice, int T, const double *v, int start, int dimension, int64_t *w,
+                               int *status)
+{
+  FPHIP_RANGE("fphip_gso_babai");
+  if (!g || !v || !w || !status)
+    return FPHIP_ERROR;
+  if (int rc = cvp_lattice_guard(g, lattice, T, "fphip_gso_babai"))
+    return rc;
+  const int d = g->P.d;
+  if (start < 0 || start >= d)
+    return gfail_msg(g->ctx, "fphip_gso_babai: start outside the basis");
+  if (dimension == -1)
+    dimension = d - start;
+  if (dimension < 1 || start + dimension > d)
+    return gfail_msg(g->ctx, "fphip_gso_babai: rows [start, start + dimension) outside the basis");
+  const size_t ldt = ((size_t)T + 63) / 64 * 64, dm = (size_t)dimension;
+  hipStream_t s = fphip_ctx_stream(g->ctx);
+  CvpBufs B(s);
+  double *bfd = nullptr, *mu = nullptr, *rd = nullptr;
+  if (int rc = cvp_unscale(g, lattice, B, &bfd, &mu, &rd))
+    return rc;
+  double *vd = nullptr, *wx = nullptr;
+  long long *wd = nullptr;
+  int *sd       = nullptr;
+  GCHK(B.get(&vd, (size_t)T * dm));
+  GCHK(B.get(&wd, (size_t)T * dm));
+  GCHK(B.get(&sd, (size_t)T));
+  GCHK(B.get(&wx, dm * ldt));
+  GCHK(hipMemcpy(vd, v, (size_t)T * dm * sizeof(double), hipMemcpyHostToDevice));
+  GCHK(hipStreamSynchronize(nullptr));
+  GCHK(hipEventRecord(g->ev[0], s));
+  hipLaunchKernelGGL(cvp_babai_kernel, dim3((unsigned)(ldt / 64)), dim3(64), 0, s, T, (int)ldt, d, start, dimension, mu, vd,
+                     wd, sd, wx);
+  GCHK(hipGetLastError());
+  GCHK(hipEventRecord(g->ev[1], s));
+  GCHK(hipStreamSynchronize(s));
+  GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  GCHK(hipMemcpy(w, wd, (size_t)T * dm * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(status, sd, (size_t)T * sizeof(int), hipMemcpyDeviceToHost));
+  return FPHIP_OK;
+}
+
+namespace
+{
+// FastEvaluator(1), EVALSTRATEGY_BEST_N_SOLUTIONS: keep the closest candidate, the bound follows it
+struct CvpBest
+{
+  int d;
+  bool have;
+  double dist;
+  std::vector<double> x;
+};
+double cvp_best_cb(void *user, double dist, const double *sol)
+{
+  CvpBest *b = (CvpBest *)user;
+  if (!b->have || dist < b->dist)
+  {
+    b->have = true;
+    b->dist = dist;
+    b->x.assign(sol, sol + b->d);
+  }
+  return b->dist;
+}
+}  // namespace
+
+// closest_vector(b, int_target, sol_coord, CVPM_FAST) (svpcvp.cpp:532-659) for T targets against one lattice:
+// update_gso, the preparation kernel over all targets, one closest-vector enumeration per target on ectx under a
+// BEST_N(1) evaluator, sol_coord = coef + x.  The enumeration starts from the rounding descent's squared distance
+// enlarged by a relative 2^-30, not from the reference's sum of the r_ii (:601-606): the descent's leaf is the first
+// one the reference reaches and lies inside either radius, so the closest vector is the same, and the top of the
+// parallel walk runs under the INITIAL radius.  Nothing inside the radius (the descent's own leaf can miss it by the
+// rounding of another operand order): the answer is the descent.
+extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets, int method,
+                                    int64_t *sol_coord, double *dist, int *status)
+{
+  FPHIP_RANGE("fphip_closest_vector");
+  if (!g || !targets || !sol_coord || !status)
+    return FPHIP_ERROR;
+  if (!ectx)
+    ectx = g->ctx;
+  if (int rc = cvp_lattice_guard(g, lattice, T, "fphip_closest_vector"))
+    return rc;
+  if (method != FPHIP_CVPM_FAST)
+  {
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: method %d (CVPM_PROVED and its max_indices reset "
+             "path, or an unknown one) is not offered: CVPM_FAST only", method);
+    return FPHIP_UNSUPPORTED;
+  }
+  const int d = g->P.d;
+  if (d > FPHIP_ENUM_MAX_DIM)
+  {
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: more than %d rows", FPHIP_ENUM_MAX_DIM);
+    return FPHIP_UNSUPPORTED;
+  }
+  std::vector<int> gst(g->P.batch, 0);
+  if (int rc = fphip_gso_update(g, gst.data()))
+    return rc;
+  if (gst[lattice] != 1)
+    return gfail_msg(g->ctx, "fphip_closest_vector: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
+  const size_t dd = (size_t)d;
+  std::vector<int64_t> coef((size_t)T * dd);
+  std::vector<double> tc((size_t)T * dd), desc((size_t)T), mu(dd * dd), rd(dd), mut(dd * dd, 0.0), xr(dd);
+  std::vector<int> pst((size_t)T);
+  if (int rc = cvp_prepare_run(g, lattice, T, targets, coef.data(), tc.data(), desc.data(), pst.data(), mu.data(), rd.data()))
+    return rc;
+  const float prep_ms = g->last_ms;
+  for (size_t i = 0; i < dd; ++i)
+    for (size_t j = i + 1; j < dd; ++j)
+      mut[i * dd + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
+  std::vector<uint64_t> nodes(dd + 1);
+  for (int t = 0; t < T; ++t)
+  {
+    int64_t *out = sol_coord + (size_t)t * dd;
+    memset(out, 0, dd * sizeof(int64_t));
+    if (dist)
+      dist[t] = 0.0;
+    status[t] = pst[t];
+    if (pst[t] != 1)
+      continue;
+    const double *c = tc.data() + (size_t)t * dd;
+    CvpBest best{d, false, 0.0, {}};
+    if (d >= 2 && desc[t] > 0.0)
+    {
+      fphip_enum_opts o;
+      memset(&o, 0, sizeof o);
+      o.shard_count     = 1;
+      o.exchange_chunks = 1;
+      o.target          = c;
+      const double maxdist = desc[t] + desc[t] * 0x1p-30;
+      // (blocks above 64 rows: the enumerator's closest-vector mode takes them on request only; the solver asks)
+      const int wide_was = fphip_ctx_allow_wide_target(ectx, 1);
+      const int rc = fphip_enum_run(ectx, d, maxdist, mut.data(), rd.data(), nullptr, &o, cvp_best_cb, nullptr, &best,
+                                    nodes.data(), nullptr);
+      fphip_ctx_allow_wide_target(ectx, wide_was);
+      if (rc != FPHIP_OK)
+      {
+        if (ectx != g->ctx)
+          snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: enumeration of target %d: %s", t,
+                   fphip_last_error(ectx));
+        return rc;
+      }
+    }
+    double bd = desc[t];
+    if (best.have)
+    {
+      xr = best.x;
+      bd = best.dist;
+    }
+    else  // the descent itself (the same loop as the kernel's)
+      for (int k = d - 1; k >= 0; --k)
+      {
+        double newcenter = c[k];
+        for (int j = k + 1; j < d; ++j)
+          newcenter -= xr[j] * mut[(size_t)k * dd + j];
+        xr[k] = std::round(newcenter);
+      }
+    for (size_t i = 0; i < dd; ++i)
+    {
+      long long xi = 0;
+      if (!(std::fabs(xr[i]) < 9223372036854775808.0) ||
+          __builtin_add_overflow((long long)coef[(size_t)t * dd + i], (long long)xr[i], &xi))
+      {
+        status[t] = -2;
+        break;
+      }
+      out[i] = xi;
+    }
+    if (status[t] != 1)
+      memset(out, 0, dd * sizeof(int64_t));
+    else if (dist)
+      dist[t] = bd;
+  }
+  g->last_ms = prep_ms;
   return FPHIP_OK;
 }
 

@@ -1,0 +1,58 @@
+"""Host-side mirror of the reference's closest-vector solver (fplll/svpcvp.cpp:532-659, ``closest_vector``).
+
+Everything is computed on the GPU behind ``fphip_closest_vector`` (include/fplll_hip.h): update_gso, the target
+preparation kernel (Gram-Schmidt coordinates, the Babai loop), one closest-vector enumeration per target; nothing here
+solves anything on the CPU.  The batched form is the workload the device is for: many targets against one reduced
+basis.
+"""
+import numpy as np
+
+from . import _lib
+from .gso import MatGSOBatch, lll_reduction
+
+CVPM_FAST = 0
+CVPM_PROVED = 2  # declined (Unsupported): the max_indices reset path of the enumeration is not offered
+RED_SUCCESS = 1
+
+
+def closest_vectors(ctx, b, targets, reduce=False, method=CVPM_FAST, ectx=None, with_dist=False):
+    """closest_vector(b, target, sol_coord, method) for every row of ``targets`` (int64 [T][n]) against the basis
+    ``b`` (int64 [d][n], d <= n), which is expected LLL-reduced as the reference expects.  ``reduce=True`` runs
+    ``lll_reduction`` first (test_cvp.cpp:43-58); the coefficients are then those in the reduced basis.
+    ``ectx``: the context the enumerations run on (None: ``ctx``).
+
+    Returns ``(sol_coord, vectors)`` — int64 [T][d] and the lattice vectors sol_coord @ b as Python-int object arrays
+    [T][n] — and with ``with_dist`` their squared distances to the targets as a third item.  A target whose numbers
+    leave the int64 range raises ``HipError`` (the caller keeps the reference's multi-precision path)."""
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    if b.ndim != 2:
+        raise ValueError("closest_vectors: b is [d][n]")
+    t = np.ascontiguousarray(targets, dtype=np.int64)
+    if t.ndim != 2 or t.shape[1] != b.shape[1]:
+        raise ValueError("closest_vectors: targets are [T][%d], got shape %r" % (b.shape[1], t.shape))
+    if reduce:
+        b, _, status, _ = lll_reduction(ctx, b, with_u=False)
+        if status != RED_SUCCESS:
+            raise _lib.HipError("closest_vectors: lll_reduction ended with status %d" % status)
+    g = MatGSOBatch(ctx, 1, b.shape[0], b.shape[1])
+    try:
+        g.set_basis(b)
+        sol, dist, st = g.closest_vector(t, ectx=ectx, method=method)
+    finally:
+        g.close()
+    bad = np.nonzero(st != RED_SUCCESS)[0]
+    if len(bad):
+        raise _lib.HipError("closest_vectors: target %d ended with status %d (-2: beyond the int64 range, -1: the "
+                            "Babai loop found no fixed point)" % (int(bad[0]), int(st[bad[0]])))
+    vec = sol.astype(object).dot(b.astype(object))
+    return (sol, vec, dist) if with_dist else (sol, vec)
+
+
+def closest_vector(ctx, b, target, reduce=False, method=CVPM_FAST, ectx=None, with_dist=False):
+    """One target: ``(sol_coord [d], vector [n])`` (and the squared distance with ``with_dist``); see
+    ``closest_vectors``."""
+    t = np.ascontiguousarray(target, dtype=np.int64)
+    if t.ndim != 1:
+        raise ValueError("closest_vector: target is one vector of n integers")
+    out = closest_vectors(ctx, b, t[None], reduce=reduce, method=method, ectx=ectx, with_dist=with_dist)
+    return tuple(a[0] for a in out)

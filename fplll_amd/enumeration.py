@@ -105,7 +105,7 @@ def enumerate_block(ctx, mut, rdiag, pruning, maxdist, evaluator, shard_index=0,
     device's work, per level >= the reference's counts.  ``target`` (d float64s, the coordinates
     EnumerationDyn::enumerate receives as target_coord): closest-vector mode (fphip_enum_opts::target) — every x
     around the target within the bounds is a candidate, distance 0 included; not together with dual, findsubsols,
-    ordered, more than 64 rows or several ranks (``Unsupported``).
+    ordered, several ranks, or more than 64 rows unless FPHIP_CVP_WIDE=1 is set (then up to 256) (``Unsupported``).
     """
     lib = ctx.lib
     mut = np.ascontiguousarray(mut, dtype=np.float64)

@@ -554,6 +554,76 @@ class MatGSOBatch:
         return is_lll_reduced(self.get_mu_matrix(lattice), self.get_r_matrix(lattice), self.row_expo(lattice),
                               delta, eta)
 
+    # ---- closest vectors (csrc/cvp_prepare.hip): one target per lane against ONE lattice of the batch
+    def babai(self, targets, start=0, dimension=-1, lattice=0):
+        """MatGSOInterface::babai(w, v, start, dimension) (gso_interface.cpp:292-311) for a batch of vectors against
+        one lattice whose GSO is up to date (update_gso): the nearest-plane loop on the rows
+        [start, start + dimension), x[i] = rint(x[i]), x[j] -= mu(start + i, start + j) x[i].  ``targets``
+        [T][dimension] (or one vector): float coordinates — or integers, the reference's overload
+        babai(v, start, dimension), which floats them first.  Returns (w int64 [T][dimension], status[T]: 1, or -2 =
+        a coefficient beyond 63 bits); one vector in, one vector and one status out."""
+        v = np.asarray(targets)
+        single = v.ndim == 1
+        v = np.ascontiguousarray(np.atleast_2d(v), dtype=np.float64)  # (set_z: integers are floated)
+        if dimension == -1:
+            dimension = self.d - start
+        if v.shape[1] != dimension:
+            raise ValueError("babai: expected vectors of %d coordinates, got shape %r" % (dimension, v.shape))
+        T = v.shape[0]
+        w = np.zeros((T, dimension), dtype=np.int64)
+        st = np.zeros(T, dtype=np.int32)
+        fn = self.lib.fphip_gso_babai
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(fn(self.h, lattice, T, v.ctypes.data_as(ctypes.c_void_p), start, dimension,
+                     w.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p)), "babai")
+        return (w[0], int(st[0])) if single else (w, st)
+
+    def cvp_prepare(self, targets, lattice=0):
+        """What closest_vector does to its integer targets before it enumerates (fphip_cvp_prepare;
+        svpcvp.cpp:571-597) against one lattice whose GSO is up to date: ``targets`` int64 [T][n].  Returns
+        (coef int64 [T][d], target_coord [T][d], descent [T], status [T]: 1 ok, -2 beyond 63 bits, -1 loop limit)."""
+        t = np.ascontiguousarray(targets, dtype=np.int64)
+        if t.ndim != 2 or t.shape[1] != self.n:
+            raise ValueError("cvp_prepare: targets are [T][%d], got shape %r" % (self.n, t.shape))
+        T = t.shape[0]
+        coef = np.zeros((T, self.d), dtype=np.int64)
+        tc = np.zeros((T, self.d), dtype=np.float64)
+        desc = np.zeros(T, dtype=np.float64)
+        st = np.zeros(T, dtype=np.int32)
+        fn = self.lib.fphip_cvp_prepare
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+        self._chk(fn(self.h, lattice, T, *(a.ctypes.data_as(ctypes.c_void_p) for a in (t, coef, tc, desc, st))),
+                  "cvp_prepare")
+        return coef, tc, desc, st
+
+    def closest_vector(self, targets, ectx=None, method=0, lattice=0):
+        """fphip_closest_vector: closest_vector(b, target, sol_coord, CVPM_FAST) for every row of ``targets`` (int64
+        [T][n]) against one lattice; ``ectx``: the enumeration context (None: this object's).  Returns
+        (sol_coord int64 [T][d], dist [T], status [T])."""
+        t = np.ascontiguousarray(targets, dtype=np.int64)
+        if t.ndim != 2 or t.shape[1] != self.n:
+            raise ValueError("closest_vector: targets are [T][%d], got shape %r" % (self.n, t.shape))
+        T = t.shape[0]
+        sol = np.zeros((T, self.d), dtype=np.int64)
+        dist = np.zeros(T, dtype=np.float64)
+        st = np.zeros(T, dtype=np.int32)
+        fn = self.lib.fphip_closest_vector
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        rc = fn(self.h, None if ectx is None else ectx.handle, lattice, T, t.ctypes.data_as(ctypes.c_void_p), method,
+                sol.ctypes.data_as(ctypes.c_void_p), dist.ctypes.data_as(ctypes.c_void_p),
+                st.ctypes.data_as(ctypes.c_void_p))
+        if rc == _lib.FPHIP_UNSUPPORTED:
+            from .enumeration import Unsupported
+            err = self.ctx.last_error()
+            raise Unsupported("closest_vector declined by the device layer (d=%d): %s" % (self.d, err))
+        self._chk(rc, "closest_vector")
+        return sol, dist, st
+
     @property
     def last_kernel_ms(self):
         return float(self.lib.fphip_gso_last_kernel_ms(self.h))

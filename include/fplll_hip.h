@@ -181,7 +181,10 @@ typedef struct fphip_enum_stats
  * closest-vector call is never declined for being small.  fphip_enum_lower_bound and the callback's bound protocol
  * are unchanged.  v1 limits, each declined with FPHIP_UNSUPPORTED and a fphip_last_error text before anything is
  * launched: target together with dual (the reference refuses that too, enumerate.cpp:73), with findsubsols, with
- * ordered, with dim > 64, with shard_count > 1, exchange or gather.  A non-finite target coordinate is FPHIP_ERROR.
+ * ordered, with shard_count > 1, exchange or gather; with dim > 64 unless FPHIP_CVP_WIDE=1 is set in the environment
+ * (opt-in: blocks of 65 .. FPHIP_ENUM_MAX_DIM rows are then walked like those of a shortest-vector call, by the top
+ * walk compiled for the mode; fphip_closest_vector opts in for its own enumerations); larger ones are declined like a
+ * shortest-vector call.  A non-finite target coordinate is FPHIP_ERROR.
  */
 int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const double *mut, const double *rdiag,
                    const double *pruning, const fphip_enum_opts *opts, fphip_sol_cb cb,
@@ -534,6 +537,46 @@ int fphip_gso_get_r(fphip_gso *g, int lattice, double *r);
 int fphip_gso_get_row_expo(fphip_gso *g, int lattice, int64_t *row_expo);
 /* duration of the last sweep kernel, HIP events on the launch stream */
 double fphip_gso_last_kernel_ms(const fphip_gso *g);
+
+/* ---- closest vectors (csrc/cvp_prepare.hip) -------------------------------------------------------
+ * All three work against ONE lattice of the batch object and a BATCH of T targets, one target per lane.
+ *
+ * fphip_cvp_prepare: what closest_vector does to an integer target before it enumerates (svpcvp.cpp:571-597), on a
+ * lattice whose Gram-Schmidt data is up to date (fphip_gso_update).  targets [T][n] int64.  Per target: get_gscoords
+ * (:494-515), the nearest-plane loop from the last row down (:524-529, ties away from zero like mpfr_round), the
+ * rounded vector added to coef and subtracted from the integer target, until every rounded coordinate lies in
+ * [-1, 1].  coef [T][d]: the accumulated coefficients.  target_coord [T][d]: get_gscoords of the reduced target,
+ * what :597 hands the enumerator.  descent [T]: the squared distance of the rounding descent from target_coord
+ * (prepare_enumeration's operand order, enumerate.cpp:167-215).  Plain double in the order of the reference's loops,
+ * on the TRUE mu and r (the row exponents applied, get_mu_exp / get_r_exp); the reference runs this step in MPFR, so
+ * these doubles are specified by tests/cvp_solver_cases.py (bit for bit), the solver's integer result by the
+ * reference.  status [T]: 1 ok; -2 a coordinate, a coefficient or an entry of the running target left the 63-bit
+ * range (the caller falls back; that target's outputs are zero); -1 no fixed point after 0x100 passes (where the
+ * reference starts to warn, :573).  fphip_gso_last_kernel_ms: the preparation kernel.
+ *
+ * fphip_gso_babai: MatGSOInterface::babai(w, v, start, dimension) (gso_interface.cpp:292-311) — the nearest-plane
+ * loop alone, one pass, on the rows [start, start + dimension) (dimension -1: to the last row), rounding like
+ * FP_NR<double>::rnd (rint).  v [T][dimension] doubles, w [T][dimension] int64; status as above.
+ *
+ * fphip_closest_vector: closest_vector(b, int_target, sol_coord, CVPM_FAST) (svpcvp.cpp:532-659) for each of the T
+ * targets — update_gso, the preparation, one closest-vector enumeration (fphip_enum_run with opts.target) per target
+ * on `ectx` (NULL: the context of g) under a BEST_N(1) evaluator, one target after another, sol_coord = coef + x.
+ * The basis is expected LLL-reduced, as the reference expects.  The enumeration starts from descent (1 + 2^-30), not
+ * from the reference's sum of the r_ii (:601-606): the descent's leaf is the first the reference reaches and lies
+ * inside either radius, so the closest vector is the same; where nothing lies inside the radius (or descent is 0:
+ * the target is a lattice point) the answer is the descent itself.  sol_coord [T][d]; dist [T] (nullable): the
+ * squared distance of the answer to the target.  status [T]: 1 RED_SUCCESS, or the preparation's -2 / -1
+ * (sol_coord zero).  method: FPHIP_CVPM_FAST only; CVPM_PROVED (its max_indices reset path) and anything else return
+ * FPHIP_UNSUPPORTED with a text.  Blocks the closest-vector enumeration declines (fphip_enum_run) are declined here
+ * with its text. */
+#define FPHIP_CVPM_FAST 0
+#define FPHIP_CVPM_PROVED 2
+int fphip_cvp_prepare(fphip_gso *g, int lattice, int T, const int64_t *targets, int64_t *coef, double *target_coord,
+                      double *descent, int *status);
+int fphip_gso_babai(fphip_gso *g, int lattice, int T, const double *v, int start, int dimension, int64_t *w,
+                    int *status);
+int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets, int method,
+                         int64_t *sol_coord, double *dist, int *status);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Batched Householder R-factor: MatHouseholder<Z_NR<long>, FP_NR<double>> (householder.h:38)    */
