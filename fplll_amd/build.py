@@ -12,8 +12,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 
-HIP_SOURCES = ["enum_kernel.hip", "enum_walk.hip", "enum_kernel_cvp.hip", "enum_walk_cvp.hip", "enum_walk4.hip", "enum_deal.hip", "enum_order.hip", "enum_host.hip", "gso_kernel.hip", "gso_sweep2.hip", "lll_kernel.hip", "lll_kernel_early.hip", "hlll_kernel.hip", "hh_blocked.hip", "hh_rows.hip", "hlll_x.hip", "lll_x.hip", "bkz_kernel.hip", "bkzs_kernel.hip", "bkz_kernel_u.hip", "bkzs_kernel_u.hip", "hlll_kernel_u.hip", "hlll_x_u.hip", "lll_x_u.hip", "gso_host.hip", "cvp_prepare.hip", "pruner_volume.hip", "pruner_search.hip", "gso_util_host.hip"]
-HIP_HEADERS = ["dev_mem.h", "dev_cache.h", "trace.h", "pruner_tables.h", "pruner_engine.h", "enum_device.h", "enum_order.h", "enum_wave.h", "gso_device.h", "gso_wave.h", "gso_sweep2.h", "ftx.h", "lll_wave.h", "lll_stream.h", os.path.join(ROOT, "include", "fplll_hip.h")]
+HIP_SOURCES = ["enum_kernel.hip", "enum_walk.hip", "enum_kernel_cvp.hip", "enum_walk_cvp.hip", "enum_walk4.hip", "enum_deal.hip", "enum_order.hip", "enum_host.hip", "gso_kernel.hip", "gso_sweep2.hip", "lll_kernel.hip", "lll_kernel_early.hip", "hlll_kernel.hip", "hh_blocked.hip", "hh_rows.hip", "hlll_x.hip", "lll_x.hip", "bkz_kernel.hip", "bkzs_kernel.hip", "bkz_kernel_u.hip", "bkzs_kernel_u.hip", "hlll_kernel_u.hip", "hlll_x_u.hip", "lll_x_u.hip", "gso_host.hip", "lll_gram.hip", "gram_host.hip", "cvp_prepare.hip", "pruner_volume.hip", "pruner_search.hip", "gso_util_host.hip"]
+HIP_HEADERS = ["dev_mem.h", "dev_cache.h", "trace.h", "pruner_tables.h", "pruner_engine.h", "enum_device.h", "enum_order.h", "enum_wave.h", "gso_device.h", "gram_device.h", "gso_wave.h", "gso_sweep2.h", "ftx.h", "lll_wave.h", "lll_stream.h", os.path.join(ROOT, "include", "fplll_hip.h")]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17",
     "-ffp-contract=off",  # fplll's arithmetic is separate mul/add (nr/nr_FP_d.inl:178); no FMA
@@ -47,6 +47,7 @@ PER_FILE_FLAGS = {
     # (100.5 -> 104.6 lattices/s at d = 120, batch 1024), outputs unchanged (parity tests)
     "lll_kernel.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
     "lll_kernel_early.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
+    "lll_gram.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],  # (the quadratic-form twin: the same loops)
     "bkz_kernel.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
     "hlll_kernel.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
     # the HLLL kernel with the transformation matrix: the same text compiled a second time (FPHIP_HLLL_U), the flags

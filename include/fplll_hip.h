@@ -663,6 +663,40 @@ int fphip_hh_get_R(fphip_hh *h, int lattice, double *R);
 int fphip_hh_get_row_expo(fphip_hh *h, int lattice, int64_t *row_expo);
 double fphip_hh_last_kernel_ms(const fphip_hh *h);
 
+/* ---- quadratic forms (csrc/lll_gram.hip, csrc/gram_host.hip) ------------------------------------
+ * A batch of d x d integer Gram matrices, each the state of a MatGSOGram<Z_NR<long>, FP_NR<double>>(g, u, u_inv_t,
+ * GSO_INT_GRAM) (fplll/gso_gram.h): a lattice given as a quadratic form has no integer basis, the results are the
+ * reduced form and the transformation u with g_out = u g_in u^T.  d <= 256; larger: FPHIP_UNSUPPORTED.
+ *
+ * fphip_gram_set takes g[batch][d][d]; an entry that is not symmetric is refused (FPHIP_ERROR and a
+ * fphip_last_error text, nothing is uploaded).  fphip_gram_broadcast puts ONE form g[d][d] into every entry.
+ * fphip_gram_get returns the forms, both triangles (after fphip_gram_lll: the reduced forms, as lll()'s
+ * symmetrize_g leaves them).
+ * fphip_gram_update: MatGSOInterface::update_gso() of every form; status (nullable) [batch] is 1, or 0 where a mu is
+ * not finite.  fphip_gram_get_mu / _get_r: [batch][d][d], mu(i, j) for j < i and r(i, j) for j <= i, 0 elsewhere
+ * (no row exponents: the values are the true ones).
+ * fphip_gram_enable_transform: u is tracked from now on; every fphip_gram_lll starts it as the identity, as a fresh
+ * MatGSOGram on a fresh u does, and fphip_gram_get_transform returns u[batch][d][d] of the last one.  u_inv_t is not
+ * offered.
+ * fphip_gram_lll: LLLReduction<Z_NR<long>, FP_NR<double>>(m, delta, eta, flags).lll() on every form, then
+ * update_gso() of the results.  flags are fplll's LLLFlags: LLL_VERBOSE (1) is ignored, LLL_EARLY_RED (2) is
+ * accepted and has no effect, as in the reference with an integer Gram matrix (lll.cpp:31-35), LLL_SIEGEL (4) is
+ * honoured.  status / info as fphip_gso_lll.  int64 entries wrap like Z_NR<long>: results equal the reference's
+ * wherever the reference itself does not overflow (DESIGN.md 4i gives the bound). */
+typedef struct fphip_gram fphip_gram;
+int fphip_gram_create(fphip_ctx *ctx, int batch, int d, fphip_gram **out);
+void fphip_gram_destroy(fphip_gram *h);
+int fphip_gram_set(fphip_gram *h, const int64_t *g);
+int fphip_gram_broadcast(fphip_gram *h, const int64_t *g);
+int fphip_gram_get(fphip_gram *h, int64_t *g_out);
+int fphip_gram_update(fphip_gram *h, int *status);
+int fphip_gram_get_mu(fphip_gram *h, double *mu);
+int fphip_gram_get_r(fphip_gram *h, double *r);
+int fphip_gram_enable_transform(fphip_gram *h);
+int fphip_gram_get_transform(fphip_gram *h, int64_t *u);
+int fphip_gram_lll(fphip_gram *h, double delta, double eta, int flags, int *status, int *info);
+double fphip_gram_last_kernel_ms(const fphip_gram *h);
+
 #ifdef __cplusplus
 }
 #endif
