@@ -91,6 +91,19 @@ struct TaskBuf
   unsigned int cap;
 };
 
+// The sink of a list call (fphip_enum_list; the kernels compiled with FPHIP_LIST): every candidate of a walk under
+// a radius that never moves, kept on the device.  An append takes `count` as its ticket — like TaskBuf::count it may
+// exceed cap: a record whose index is >= cap is not written, the count stays exact.  Row i of x holds the d
+// coefficients of record i (lane = level); the lanes beyond a row store into the 64 doubles behind x[cap][d].
+struct ListBuf
+{
+  double *dist;               // [cap]
+  double *x;                  // [cap][d] + 64 doubles of padding
+  unsigned long long *count;  // records appended in this call
+  unsigned long long cap;
+  int d;
+};
+
 // Queue memory of one enumeration call (device; zeroed at the start of the call).
 struct QueueMem
 {

@@ -62,6 +62,31 @@ __global__ void enum_walk_cvp_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskB
                                      unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
                                      unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
                                      const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
+// list mode (fphip_enum_list): the same kernel texts compiled with the device-resident list as their sink
+// (enum_kernel_list.hip, enum_walk_list.hip and their closest-vector twins)
+template <bool MU_LDS, bool SUBS, bool DUAL>
+__global__ void enum_phase_list_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, int stop,
+                                       unsigned task_lo, unsigned task_hi, const unsigned *idxlist, int launch_idx,
+                                       int count_nodes, unsigned budget, const double *xhi_root, double *gstk, int Tsplit,
+                                       unsigned *qh, const unsigned *rcnt, unsigned rcap, unsigned long long bound_init,
+                                       ListBuf lst);
+template <bool MU_LDS, bool SUBS, bool DUAL>
+__global__ void enum_phase_cvp_list_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, int stop,
+                                           unsigned task_lo, unsigned task_hi, const unsigned *idxlist, int launch_idx,
+                                           int count_nodes, unsigned budget, const double *xhi_root, double *gstk,
+                                           int Tsplit, unsigned *qh, const unsigned *rcnt, unsigned rcap,
+                                           unsigned long long bound_init, ListBuf lst);
+template <bool MU_LDS, bool DUAL, bool CHAIN>
+__global__ void enum_walk_list_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, unsigned task_lo,
+                                      unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
+                                      unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
+                                      const unsigned *rcnt, unsigned rcap, unsigned long long bound_init, ListBuf lst);
+template <bool MU_LDS, bool DUAL, bool CHAIN>
+__global__ void enum_walk_cvp_list_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax,
+                                          unsigned task_lo, unsigned task_hi, const unsigned *idxlist, int launch_idx,
+                                          int count_nodes, unsigned budget, const double *xhi_root, double *gstk, int Tsplit,
+                                          unsigned *qh, const unsigned *rcnt, unsigned rcap, unsigned long long bound_init,
+                                          ListBuf lst);
 template <bool DUAL>
 __global__ void enum_bfs_cvp_kernel(DevShared *g, double maxdist, QueueMem *qm, TaskBuf f0, TaskBuf f1, TaskBuf fin, int L0,
                                     int nlev, int floor_level, float heavy, int count_nodes, int compact_n, int shard_index,
@@ -220,7 +245,7 @@ static int fail(fphip_ctx *ctx, const char *fmt, ...)
       return fail(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" int fphip_abi_version(void) { return 4; }
+extern "C" int fphip_abi_version(void) { return 5; }
 
 extern "C" int fphip_device_count(void)
 {
@@ -810,11 +835,25 @@ extern "C" int fphip_debug_order_replay(int dim, double maxdist, const double *m
   return (int)rp.delivered;
 }
 
+// The launch schedule of an enumeration call.  lst == nullptr: fphip_enum_run.  Otherwise a list call
+// (fphip_enum_list): the same schedule with the kernels compiled for the mode, whose candidates stay in *lst on the
+// device — `cb` is never called, the radius never moves, and lst->count is reset wherever the call starts over.
+static int enum_run_impl(fphip_ctx *ctx, int dim, double maxdist, const double *mut, const double *rdiag,
+                         const double *pruning, const fphip_enum_opts *opts_in, fphip_sol_cb cb, fphip_subsol_cb subcb,
+                         void *user, uint64_t *nodes_out, fphip_enum_stats *stats, const ListBuf *lst);
+
 extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const double *mut,
                               const double *rdiag, const double *pruning,
                               const fphip_enum_opts *opts_in, fphip_sol_cb cb,
                               fphip_subsol_cb subcb, void *user, uint64_t *nodes_out,
                               fphip_enum_stats *stats)
+{
+  return enum_run_impl(ctx, dim, maxdist, mut, rdiag, pruning, opts_in, cb, subcb, user, nodes_out, stats, nullptr);
+}
+
+static int enum_run_impl(fphip_ctx *ctx, int dim, double maxdist, const double *mut, const double *rdiag,
+                         const double *pruning, const fphip_enum_opts *opts_in, fphip_sol_cb cb, fphip_subsol_cb subcb,
+                         void *user, uint64_t *nodes_out, fphip_enum_stats *stats, const ListBuf *lst)
 {
   FPHIP_RANGE("fphip_enum_run");
   if (!ctx)
@@ -836,7 +875,14 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
   if (o.exchange_chunks <= 0)
     o.exchange_chunks = 1;
   const int d = dim;
-  if (d < 2 || d > FPHIP_ENUM_MAX_DIM || (o.findsubsols && !subcb))
+  if (lst && (d < 1 || d > 64 || o.shard_count > 1 || o.exchange || o.gather || o.dual || o.findsubsols || o.ordered))
+  {  // list mode, v1: the top walk is not compiled for it; one rank; candidates only, in the device's own order
+    snprintf(ctx->err, sizeof ctx->err, "list enumeration: not with %s",
+             d > 64 ? "more than 64 rows" : d < 1 ? "less than one row" : (o.dual || o.findsubsols || o.ordered)
+                 ? "dual, findsubsols or ordered" : "several ranks (shard_count, exchange, gather)");
+    return FPHIP_UNSUPPORTED;
+  }
+  if (d < (lst ? 1 : 2) || d > FPHIP_ENUM_MAX_DIM || (o.findsubsols && !subcb))
   {
     if (d > FPHIP_ENUM_MAX_DIM)
       snprintf(ctx->err, sizeof ctx->err, "enumeration: more than %d rows", FPHIP_ENUM_MAX_DIM);
@@ -924,7 +970,8 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
   // Breadth-first stage instead of the depth-first split launches (see enum_bfs_kernel): the default;
   // sub-solution calls keep the split launches (the expansion does not report sub-solutions), and a
   // call whose expansion overflowed a buffer starts over with them.
-  bool use_bfs = env_int("FPHIP_BFS", 1) != 0 && !subs;
+  // (a block of one row — list calls only — has no level to expand: its root task goes straight to a walk launch)
+  bool use_bfs = env_int("FPHIP_BFS", 1) != 0 && !subs && d >= 2;
   int bfs_restarts = 0;
   // ordered: the ring consumer stores the candidates, the caller's callback is only called by the replay
   OrderReplay ost;
@@ -945,6 +992,11 @@ extern "C" int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const dou
     ost.init(d, mut, rdiag, pruning, maxdist);
     cb_dev  = order_collect_cb;
     user_dev = &ost;
+    __atomic_store_n(&ctx->ordered_running, 1, __ATOMIC_RELEASE);
+    ordered_flag.p = &ctx->ordered_running;
+  }
+  if (lst)
+  {  // a list call runs under ONE radius: a foreign bound (fphip_enum_lower_bound) is ignored, as for an ordered call
     __atomic_store_n(&ctx->ordered_running, 1, __ATOMIC_RELEASE);
     ordered_flag.p = &ctx->ordered_running;
   }
@@ -1010,6 +1062,8 @@ restart:
   __atomic_store_n(&ctx->h->consumed, ctx->ring_next, __ATOMIC_RELEASE);
   HIPCHK(ctx, hipMemcpyAsync(ctx->g, st, st_used, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->qm, 0, sizeof(QueueMem), ctx->stream));
+  if (lst)  // (every path that starts the call over comes through here: no record of the abandoned pass is seen twice)
+    HIPCHK(ctx, hipMemsetAsync(lst->count, 0, sizeof(unsigned long long), ctx->stream));
   // root task: level d, zero partial sums, zero prefix, zero partial distance (the breadth-first
   // stage reads its first frontier from buf[1] and leaves the final task list in buf[0])
   int cur = use_bfs ? 1 : 0;
@@ -1612,7 +1666,50 @@ restart:
     else                                                                                             \
       FPHIP_LAUNCH2_K(M, D, false);                                                                  \
   } while (0)
-        if (cvp)
+        // list mode: the same choice among the kernels compiled for it (the arguments of their twins, then the list)
+#define FPHIP_LAUNCH_LIST(KERNEL, M)                                                                 \
+  hipLaunchKernelGGL((KERNEL<M, false, false>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
+                     ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, stop, lo, hi, idxl, launch_idx,     \
+                     count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],  \
+                     regioned ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ,   \
+                     (unsigned long long)dbits(maxdist), *lst)
+#define FPHIP_LAUNCH2_LIST(KERNEL, M, C)                                                             \
+  hipLaunchKernelGGL((KERNEL<M, false, C>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g,    \
+                     ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,           \
+                     count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0],  \
+                     regioned ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ,   \
+                     (unsigned long long)dbits(maxdist), *lst)
+        if (lst)
+        {
+          if (in_final && walk2)
+          {
+            if (cvp && mu_lds && walk3)
+              FPHIP_LAUNCH2_LIST(enum_walk_cvp_list_kernel, true, true);
+            else if (cvp && mu_lds)
+              FPHIP_LAUNCH2_LIST(enum_walk_cvp_list_kernel, true, false);
+            else if (cvp && walk3)
+              FPHIP_LAUNCH2_LIST(enum_walk_cvp_list_kernel, false, true);
+            else if (cvp)
+              FPHIP_LAUNCH2_LIST(enum_walk_cvp_list_kernel, false, false);
+            else if (mu_lds && walk3)
+              FPHIP_LAUNCH2_LIST(enum_walk_list_kernel, true, true);
+            else if (mu_lds)
+              FPHIP_LAUNCH2_LIST(enum_walk_list_kernel, true, false);
+            else if (walk3)
+              FPHIP_LAUNCH2_LIST(enum_walk_list_kernel, false, true);
+            else
+              FPHIP_LAUNCH2_LIST(enum_walk_list_kernel, false, false);
+          }
+          else if (cvp && mu_lds)
+            FPHIP_LAUNCH_LIST(enum_phase_cvp_list_kernel, true);
+          else if (cvp)
+            FPHIP_LAUNCH_LIST(enum_phase_cvp_list_kernel, false);
+          else if (mu_lds)
+            FPHIP_LAUNCH_LIST(enum_phase_list_kernel, true);
+          else
+            FPHIP_LAUNCH_LIST(enum_phase_list_kernel, false);
+        }
+        else if (cvp)
         {  // closest-vector mode: the same choice among the kernels compiled for it (primal, no sub-solutions)
           if (in_final && walk2 && walk3)
           {
@@ -1661,6 +1758,8 @@ restart:
 #undef FPHIP_LAUNCH2
 #undef FPHIP_LAUNCH2_K
 #undef FPHIP_LAUNCH2_KK
+#undef FPHIP_LAUNCH_LIST
+#undef FPHIP_LAUNCH2_LIST
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         ++launch_idx;
@@ -1799,6 +1898,12 @@ restart:
                   (unsigned long long)ost.mismatched);
     nsol = ost.delivered;
   }
+  if (lst)
+  {  // (every launch has been waited for)
+    unsigned long long n = 0;
+    HIPCHK(ctx, hipMemcpy(&n, lst->count, sizeof n, hipMemcpyDeviceToHost));
+    nsol = n;
+  }
 
   // ---- results --------------------------------------------------------------------------------
   HIPCHK(ctx, hipMemcpy(st, ctx->g, offsetof(DevShared, task_head), hipMemcpyDeviceToHost));
@@ -1855,5 +1960,102 @@ restart:
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin)
             .count();
   }
+  return FPHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// List mode (fphip_enum_list)
+// ---------------------------------------------------------------------------------------------
+
+// The canonical order of a list: distance ascending, ties by the coefficients compared from level dim - 1 down to 0.
+// n records (dist_in[i], x_in[i * dim ..)) — in whatever order the device appended them — come out sorted in
+// dist_out / x_out (which must not overlap the inputs).  Host only; nothing here needs a device.
+extern "C" void fphip_list_sort_records(int dim, uint64_t n, const double *dist_in, const double *x_in, double *dist_out,
+                                        double *x_out)
+{
+  std::vector<uint64_t> perm((size_t)n);
+  for (uint64_t i = 0; i < n; ++i)
+    perm[(size_t)i] = i;
+  std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) {
+    if (dist_in[a] != dist_in[b])
+      return dist_in[a] < dist_in[b];
+    const double *xa = x_in + (size_t)a * dim, *xb = x_in + (size_t)b * dim;
+    for (int k = dim - 1; k >= 0; --k)
+      if (xa[k] != xb[k])
+        return xa[k] < xb[k];
+    return a < b;  // (equal records do not occur in a list; a total order all the same)
+  });
+  for (uint64_t i = 0; i < n; ++i)
+  {
+    dist_out[(size_t)i] = dist_in[(size_t)perm[(size_t)i]];
+    memcpy(x_out + (size_t)i * dim, x_in + (size_t)perm[(size_t)i] * dim, (size_t)dim * sizeof(double));
+  }
+}
+
+static double list_keep_bound_cb(void *user, double, const double *) { return *(const double *)user; }
+
+extern "C" int fphip_enum_list(fphip_ctx *ctx, int dim, double radius, const double *mut, const double *rdiag,
+                               const double *pruning, const double *target, uint64_t cap, double *dist, double *x,
+                               uint64_t *count, uint64_t *nodes_out, fphip_enum_stats *stats)
+{
+  if (!ctx)
+    return FPHIP_ERROR;
+  if (!ctx->g)
+    return fail(ctx, "context has no device (creation failed): %s", ctx->err);
+  if (!mut || !rdiag || !count || !nodes_out || (cap > 0 && (!dist || !x)))
+    return fail(ctx, "null argument");
+  if (dim > 64 || dim < 1)
+  {
+    snprintf(ctx->err, sizeof ctx->err, "list enumeration: not with %s", dim > 64 ? "more than 64 rows" : "less than one row");
+    return FPHIP_UNSUPPORTED;
+  }
+  if (cap > (1ull << 40) / ((uint64_t)dim * sizeof(double)))
+    return fail(ctx, "list enumeration: a capacity of %llu records is beyond any device", (unsigned long long)cap);
+  *count = 0;
+  auto t0 = std::chrono::steady_clock::now();  // (the whole call: buffers, walk, copy and sort)
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ListBuf lb;
+  memset(&lb, 0, sizeof lb);
+  lb.cap = cap;
+  lb.d   = dim;
+  struct Release
+  {
+    fphip_ctx *c;
+    ListBuf *b;
+    ~Release()
+    {
+      if (b->dist)
+        fphip_dev_free(b->dist, c->stream);
+      if (b->x)
+        fphip_dev_free(b->x, c->stream);
+      if (b->count)
+        fphip_dev_free(b->count, c->stream);
+    }
+  } release{ctx, &lb};
+  HIPCHK(ctx, fphip_dev_alloc((void **)&lb.dist, (size_t)std::max<uint64_t>(cap, 1) * sizeof(double), ctx->stream));
+  HIPCHK(ctx, fphip_dev_alloc((void **)&lb.x, ((size_t)cap * dim + 64) * sizeof(double), ctx->stream));
+  HIPCHK(ctx, fphip_dev_alloc((void **)&lb.count, 64, ctx->stream));
+  fphip_enum_opts o;
+  memset(&o, 0, sizeof o);
+  o.target = target;
+  double keep = radius;
+  fphip_enum_stats st_local;
+  memset(&st_local, 0, sizeof st_local);
+  const int rc = enum_run_impl(ctx, dim, radius, mut, rdiag, pruning, &o, list_keep_bound_cb, nullptr, &keep, nodes_out,
+                               &st_local, &lb);
+  if (rc != FPHIP_OK)
+    return rc;
+  const uint64_t n = st_local.solutions, m = std::min<uint64_t>(n, cap);
+  if (m > 0)
+  {
+    std::vector<double> hd((size_t)m), hx((size_t)m * dim);
+    HIPCHK(ctx, hipMemcpy(hd.data(), lb.dist, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(hx.data(), lb.x, (size_t)m * dim * sizeof(double), hipMemcpyDeviceToHost));
+    fphip_list_sort_records(dim, m, hd.data(), hx.data(), dist, x);
+  }
+  *count = n;
+  st_local.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (stats)
+    *stats = st_local;
   return FPHIP_OK;
 }

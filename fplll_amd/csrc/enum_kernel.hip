@@ -80,6 +80,27 @@
 #define FPHIP_PHASE_KERNEL enum_phase_kernel
 #define FPHIP_BFS_KERNEL enum_bfs_kernel
 #endif
+// List mode (FPHIP_LIST): enum_kernel_list.hip and enum_kernel_cvp_list.hip compile the text of
+// enum_phase_kernel — and of nothing else in this file — once more, into enum_phase_list_kernel /
+// enum_phase_cvp_list_kernel, for calls whose radius never moves (fphip_enum_list): a candidate is appended to a list on
+// the device (ListBuf, one more kernel argument) instead of going through the pinned ring.  Every line of it sits
+// behind the preprocessor: without the macro the text is what it was.
+#ifndef FPHIP_LIST
+#define FPHIP_LIST 0
+#endif
+#if FPHIP_LIST
+#undef FPHIP_PHASE_KERNEL
+#if FPHIP_CVP
+#define FPHIP_PHASE_KERNEL enum_phase_cvp_list_kernel
+#else
+#define FPHIP_PHASE_KERNEL enum_phase_list_kernel
+#endif
+#define FPHIP_LIST_PARAM , ListBuf lst
+#define FPHIP_LIST_TYPE , ListBuf
+#else
+#define FPHIP_LIST_PARAM
+#define FPHIP_LIST_TYPE
+#endif
 
 namespace fphip
 {
@@ -115,7 +136,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
                       const unsigned *__restrict__ idxlist, int launch_idx, int count_nodes,
                       unsigned budget, const double *__restrict__ xhi_root, double *__restrict__ gstk,
                       int Tsplit, unsigned *__restrict__ qh, const unsigned *__restrict__ rcnt, unsigned rcap,
-                      unsigned long long bound_init)
+                      unsigned long long bound_init FPHIP_LIST_PARAM)
 {
   constexpr bool CVP = FPHIP_CVP != 0;  // closest-vector mode: see the header
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -296,6 +317,24 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
 
     // Reports a candidate (process_solution) and waits for the host's verdict, like enumlib's
     // mutex-protected process_sol (enumeration.h:286-299).
+#if FPHIP_LIST
+    // List mode: the candidate is appended to the list on the device — a ticket, then the row (lane = level; the lanes
+    // beyond it land in the padding behind the buffer: a select of the address, no lane-masked branch) and the
+    // distance (every lane: the same word).  No pinned-memory write, no verdict to wait for, no bound to refresh.
+    auto report = [&](double dist)
+    {
+      const unsigned long long idx = rfl_u64(lane0_atomic_add_u64(lst.count, 1ull));
+      if (idx < lst.cap)
+      {
+        const double xf = (lane < Lt) ? xs : xpre;
+        const int rl    = here_lane(lane);
+        double *dst     = (lane < lst.d) ? lst.x + idx * (unsigned long long)lst.d + rl
+                                         : lst.x + lst.cap * (unsigned long long)lst.d + rl;
+        *dst            = xf;
+        lst.dist[idx]   = dist;
+      }
+    };
+#else
     auto report = [&](double dist)
     {
       // (no lane-masked branch in here either: the level registers are live across the report — enum_wave.h)
@@ -340,6 +379,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       }
       FPHIP_REFRESH_BOUND(true);
     };
+#endif
 
     // process_subsolution (enumerate.cpp:241-249): a node at level lvl is shorter than every
     // sub-solution seen at that level.  Only the wave that lowers the device-wide best reports;
@@ -739,10 +779,10 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
                                                       int, int, unsigned, unsigned, const unsigned *,  \
                                                       int, int, unsigned, const double *, double *, int, \
                                                       unsigned *, const unsigned *, unsigned,            \
-                                                      unsigned long long);
+                                                      unsigned long long FPHIP_LIST_TYPE);
 FPHIP_INST(true, false, false)
 FPHIP_INST(false, false, false)
-#if !FPHIP_CVP  // (a target comes without sub-solutions and without dual)
+#if !FPHIP_CVP && !FPHIP_LIST  // (a target, and a list, come without sub-solutions and without dual)
 FPHIP_INST(true, true, false)
 FPHIP_INST(false, true, false)
 FPHIP_INST(true, false, true)
@@ -750,6 +790,8 @@ FPHIP_INST(false, false, true)
 #endif
 #undef FPHIP_INST
 
+#if !FPHIP_LIST  // (a list call runs the breadth-first stage of its shortest- / closest-vector twin: nothing is
+                 //  reported up there; the top walk of blocks above 64 rows is not compiled for the mode)
 // ---------------------------------------------------------------------------------------------
 // Breadth-first expansion of the TOP of the tree.
 //
@@ -1341,5 +1383,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 #endif  // !FPHIP_CVP
+#endif  // !FPHIP_LIST
 
 }  // namespace fphip

@@ -87,10 +87,29 @@
 #ifndef FPHIP_CVP
 #define FPHIP_CVP 0
 #endif
-#if FPHIP_CVP
+// List mode (FPHIP_LIST): enum_walk_list.hip and enum_walk_cvp_list.hip compile this text once
+// more, into enum_walk_list_kernel / enum_walk_cvp_list_kernel, for calls whose radius never moves (fphip_enum_list).
+// Every candidate is appended to a list on the device (ListBuf, one more kernel argument) instead of being handed to
+// the host through the pinned ring, and the children of a level-1 node are tested 64 at a time.  Every line of it sits
+// behind the preprocessor: without the macro the text is what it was.
+#ifndef FPHIP_LIST
+#define FPHIP_LIST 0
+#endif
+#if FPHIP_LIST && FPHIP_CVP
+#define FPHIP_WALK_KERNEL enum_walk_cvp_list_kernel
+#elif FPHIP_LIST
+#define FPHIP_WALK_KERNEL enum_walk_list_kernel
+#elif FPHIP_CVP
 #define FPHIP_WALK_KERNEL enum_walk_cvp_kernel
 #else
 #define FPHIP_WALK_KERNEL enum_walk_kernel
+#endif
+#if FPHIP_LIST
+#define FPHIP_LIST_PARAM , ListBuf lst
+#define FPHIP_LIST_TYPE , ListBuf
+#else
+#define FPHIP_LIST_PARAM
+#define FPHIP_LIST_TYPE
 #endif
 // The fourth generation (enum_walk4.hip compiles this text with FPHIP_WALK4 = 1 into enum_walk4_kernel<MU_LDS, DUAL>,
 // see the header there): the third with ready pair siblings.  Every line of it sits behind the preprocessor
@@ -154,7 +173,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
                      const unsigned *__restrict__ idxlist, int launch_idx, int count_nodes,
                      unsigned budget, const double *__restrict__ xhi_root, double *__restrict__ gstk,
                      int Tsplit, unsigned *__restrict__ qh, const unsigned *__restrict__ rcnt, unsigned rcap,
-                     unsigned long long bound_init)
+                     unsigned long long bound_init FPHIP_LIST_PARAM)
 {
   constexpr bool CVP = FPHIP_CVP != 0;  // closest-vector mode: see the header
 #if FPHIP_WALK4
@@ -391,6 +410,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       }
     };
 
+#if !FPHIP_LIST  // (list mode: no record leaves the device during the walk — see the leaf pass)
     auto report = [&](double dist, double xleaf, bool &bchg)
     {
       unsigned long long idx = 0;
@@ -439,6 +459,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       }
       FPHIP_REFRESH_BOUND(true, bchg);
     };
+#endif
 
     // The bound went down: the pending siblings of the hot levels (CHAIN: hot B levels) in [klo, Lt) — inside the
     // count n of their expansion, not visited yet — are tested again, from the last one downwards (the distances are
@@ -763,6 +784,74 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
       {
         if ((unsigned)(k - elo) <= erng)
           ev = EV_EMIT;
+#if FPHIP_LIST
+        else if (k == 1)
+        {
+          // The children of a level-1 node under a radius that never moves: the leaves of a node are independent, so
+          // they are tested 64 at a time.  Sibling j of the reference's order (:80-92) sits in lane j of a pass: the
+          // zig-zag around roundto(c), or — the half tree: parent distance exactly 0, no target — the j-th step
+          // upwards.  x, al and ndc are formed as the serial loop of the other modes forms them (x by exact integer
+          // adds there, one exact add here), so a record's distance is that loop's bit for bit.  The distances do not
+          // decrease along the sequence: the survivors are a prefix of the lanes, read off one ballot.
+          const double c0 = rl_f64(S, 0);
+          double x0 = rint(c0);
+          {
+            const double al0 = x0 - c0;
+            if (fabs(al0) == 0.5 && ((al0 < 0.0) == (c0 > 0.0)))
+              x0 = x0 - (al0 + al0);
+          }
+          const bool up = __builtin_amdgcn_ballot_w64(c0 >= x0) != 0ull;
+          bool zig      = __builtin_amdgcn_ballot_w64(nd != 0.0) != 0ull;
+          if constexpr (CVP)
+            zig = true;
+          const double r0 = g->rdiag[0], p0 = g->pruning[0];
+          // the coefficients of levels >= 1: once per level-1 node that has a record (CHAIN: one path replay), not
+          // once per record
+          double xrow   = 0.0;
+          bool have_row = false;
+          for (int jb = 0;; jb += 64)
+          {
+            const int j      = jb + lane;
+            const int zj     = zig ? zig_of(j, !up) : j;
+            const double x   = x0 + (double)zj;
+            const double al  = x - c0;
+            const double ndc = nd + al * al * r0;
+            const unsigned long long ok = __builtin_amdgcn_ballot_w64(ndc <= p0 * maxdist);
+            const int n = ok == ~0ull ? 64 : __builtin_ctzll(~ok);  // (the serial loop ends at the first failure)
+            cnt += (lane == 0) ? (unsigned long long)n : 0ull;      // nodes[0] grows by n
+            // (:44 / :99: newdist > 0.0 || !is_svp — the zero leaf of the half tree is a node and not a record)
+            unsigned long long rm = __builtin_amdgcn_ballot_w64(lane < n && (CVP || ndc > 0.0));
+            if (rm != 0ull)
+            {
+              if (!have_row)
+              {
+                xrow     = path_x(1);
+                have_row = true;
+              }
+              unsigned long long base = 0;
+              if (lane == 0)
+                base = atomicAdd(lst.count, (unsigned long long)__builtin_popcountll(rm));  // ONE ticket per pass
+              base = rfl_u64(base);
+              const unsigned long long slot = base + (unsigned long long)__builtin_popcountll(rm & ((1ull << lane) - 1ull));
+              if (((rm >> lane) & 1ull) != 0ull && slot < lst.cap)
+                lst.dist[slot] = ndc;
+              FPHIP_JOIN();
+              double *pad = lst.x + lst.cap * (unsigned long long)lst.d;
+              for (unsigned long long i = base; rm != 0ull && i < lst.cap; ++i, rm &= rm - 1ull)
+              {  // the row of one record, lane = level (the lanes beyond the row land in the padding)
+                const double xl = rl_f64(x, __builtin_ctzll(rm));
+                const int rl    = here_lane(lane);
+                double *dst     = (lane < lst.d) ? lst.x + i * (unsigned long long)lst.d + rl : pad + rl;
+                *dst            = (lane == 0) ? xl : xrow;
+              }
+            }
+            if (n < 64)
+              break;
+          }
+          resume_step = true;
+          continue;
+        }
+#else
         else if (k == 1)
         {
           // the children of a level-1 node are leaves (:97-101): one by one, a reported candidate may lower
@@ -810,6 +899,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           resume_step = true;
           continue;
         }
+#endif
         else
         {
           // the expansion by hand of a slow level: the zero chain, 61+ surviving children, or a level the mask holds
@@ -988,16 +1078,17 @@ FPHIP_INST4(false, true)
   template __global__ void FPHIP_WALK_KERNEL<M, D, C>(DevShared *, HostCtl *, TaskBuf, TaskBuf, int, int, \
                                                   unsigned, unsigned, const unsigned *, int, int,       \
                                                   unsigned, const double *, double *, int, unsigned *,   \
-                                                  const unsigned *, unsigned, unsigned long long);
+                                                  const unsigned *, unsigned, unsigned long long FPHIP_LIST_TYPE);
 FPHIP_INST(true, false, false)
 FPHIP_INST(false, false, false)
-#if !FPHIP_CVP  // (no dual instantiation with a target: the reference refuses the pair, enumerate.cpp:73)
+#if !FPHIP_CVP && !FPHIP_LIST  // (no dual instantiation with a target: the reference refuses the pair,
+                               //  enumerate.cpp:73; a list call has no dual form)
 FPHIP_INST(true, true, false)
 FPHIP_INST(false, true, false)
 #endif
 FPHIP_INST(true, false, true)
 FPHIP_INST(false, false, true)
-#if !FPHIP_CVP
+#if !FPHIP_CVP && !FPHIP_LIST
 FPHIP_INST(true, true, true)
 FPHIP_INST(false, true, true)
 #endif

@@ -199,5 +199,19 @@ struct CvpPrep
   long long *wt;  // [n][ldt] the running integer target
   long long *wk;  // [d][ldt] the accumulated coefficients
 };
+
+// records of a list enumeration -> lattice vectors and exact norms (list_vectors.hip): one record per lane
+struct ListVec
+{
+  int m, ldt;  // number of records; lanes per workspace row (m rounded up to 64)
+  int d, n, ldn;
+  const long long *b;       // [d][ldn] the lattice's integer basis
+  const long long *coef;    // [m][d]   the records' coefficients
+  const long long *target;  // [n] or null: subtracted from every vector
+  long long *vec;           // [m][n]
+  long long *norm;          // [m]      |vec|^2, exact
+  int *status;              // [m]      1 ok, -2 beyond 63 bits (outputs zero)
+  long long *wv;            // [n][ldt] workspace, one column per lane
+};
 }  // namespace fphip
 #endif

@@ -116,6 +116,7 @@ __global__ void lll_kernel(GsoBatch P, int kmin, int kstart, int kend, double de
 // cvp_prepare.hip: the closest-vector solver's target preparation and MatGSOInterface::babai, one target per lane
 __global__ void cvp_unscale_kernel(GsoBatch P, int lattice, double *bfd, double *mu, double *rd);
 __global__ void cvp_prepare_kernel(CvpPrep P);
+__global__ void list_vectors_kernel(ListVec P);  // list_vectors.hip
 __global__ void cvp_babai_kernel(int T, int ldt, int d, int start, int dimension, const double *mu, const double *v,
                                  long long *w, int *status, double *wx);
 }
@@ -3340,6 +3341,178 @@ extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, 
       dist[t] = bd;
   }
   g->last_ms = prep_ms;
+  return FPHIP_OK;
+}
+
+// ---- lists of short / near vectors (list_vectors.hip; the enumeration: fphip_enum_list) ----------------------------
+// the vector kernel over m records of one lattice: vec [m][n], norm [m], status [m]
+static int list_vectors_run(fphip_gso *g, int lattice, uint64_t m, const int64_t *coef, const int64_t *target, int64_t *vec,
+                            int64_t *norm, int *status)
+{
+  const size_t d = g->P.d, n = g->P.n, ldt = ((size_t)m + 63) / 64 * 64;
+  hipStream_t s = fphip_ctx_stream(g->ctx);
+  CvpBufs B(s);
+  ListVec P;
+  memset(&P, 0, sizeof P);
+  long long *cd = nullptr, *td = nullptr;
+  GCHK(B.get(&cd, (size_t)m * d));
+  GCHK(B.get(&td, n));
+  GCHK(B.get(&P.vec, (size_t)m * n));
+  GCHK(B.get(&P.norm, (size_t)m));
+  GCHK(B.get(&P.status, (size_t)m));
+  GCHK(B.get(&P.wv, n * ldt));
+  GCHK(hipMemcpy(cd, coef, (size_t)m * d * sizeof(long long), hipMemcpyHostToDevice));
+  if (target)
+    GCHK(hipMemcpy(td, target, n * sizeof(long long), hipMemcpyHostToDevice));
+  GCHK(hipStreamSynchronize(nullptr));  // (see fphip_gso_set_basis)
+  P.m = (int)m, P.ldt = (int)ldt, P.d = (int)d, P.n = (int)n, P.ldn = g->P.ldn;
+  P.b      = g->P.b + (size_t)lattice * d * g->P.ldn;
+  P.coef   = cd;
+  P.target = target ? td : nullptr;
+  GCHK(hipEventRecord(g->ev[0], s));
+  hipLaunchKernelGGL(list_vectors_kernel, dim3((unsigned)(ldt / 64)), dim3(64), 0, s, P);
+  GCHK(hipGetLastError());
+  GCHK(hipEventRecord(g->ev[1], s));
+  GCHK(hipStreamSynchronize(s));
+  GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  GCHK(hipMemcpy(vec, P.vec, (size_t)m * n * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(norm, P.norm, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(status, P.status, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_list_records_to_vectors(fphip_gso *g, int lattice, uint64_t m, const int64_t *coef,
+                                             const int64_t *target, int64_t *vec, int64_t *norm, int *status)
+{
+  FPHIP_RANGE("fphip_list_records_to_vectors");
+  if (!g || !coef || !vec || !norm || !status)
+    return FPHIP_ERROR;
+  if (int rc = cvp_lattice_guard(g, lattice, m > 0 && m < (1ull << 31) ? 1 : 0, "fphip_list_records_to_vectors"))
+    return rc;
+  return list_vectors_run(g, lattice, m, coef, target, vec, norm, status);
+}
+
+// Every lattice vector v of one lattice with |v - t|^2 <= bound_sq, exactly: update_gso, the true mu and r, with a
+// target its Gram-Schmidt coordinates (get_gscoords, the operation sequence of cvp_prepare_kernel; no Babai
+// reduction: the radius is the caller's), a list enumeration at bound_sq (1 + 2^-30), the vector kernel, and the
+// filter norm <= bound_sq on the exact integers.  The 2^-30 is the margin of fphip_closest_vector: a heuristic
+// allowance for the rounding of the enumeration's doubles, not a proved error bound (the reference enlarges its
+// radius by get_max_error_aux there).
+extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, const int64_t *target, int64_t bound_sq,
+                                  uint64_t cap, int64_t *coef, int64_t *vec, int64_t *norm, uint64_t *count)
+{
+  FPHIP_RANGE("fphip_list_vectors");
+  if (!g || !count || (cap > 0 && (!coef || !vec || !norm)))
+    return FPHIP_ERROR;
+  if (!ectx)
+    ectx = g->ctx;
+  *count = 0;
+  if (int rc = cvp_lattice_guard(g, lattice, 1, "fphip_list_vectors"))
+    return rc;
+  if (bound_sq < 0)
+    return gfail_msg(g->ctx, "fphip_list_vectors: a negative bound");
+  const int d = g->P.d;
+  const size_t dd = (size_t)d, n = (size_t)g->P.n;
+  if (d > 64)
+  {
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_list_vectors: more than 64 rows (list enumeration)");
+    return FPHIP_UNSUPPORTED;
+  }
+  std::vector<int> gst(g->P.batch, 0);
+  if (int rc = fphip_gso_update(g, gst.data()))
+    return rc;
+  if (gst[lattice] != 1)
+    return gfail_msg(g->ctx, "fphip_list_vectors: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
+  std::vector<double> mu(dd * dd), rd(dd), bfd(dd * n), mut(dd * dd, 0.0), tc(dd, 0.0);
+  {
+    hipStream_t s = fphip_ctx_stream(g->ctx);
+    CvpBufs B(s);
+    double *bfd_d = nullptr, *mu_d = nullptr, *rd_d = nullptr;
+    if (int rc = cvp_unscale(g, lattice, B, &bfd_d, &mu_d, &rd_d))
+      return rc;
+    GCHK(hipStreamSynchronize(s));
+    GCHK(hipMemcpy(mu.data(), mu_d, dd * dd * sizeof(double), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(rd.data(), rd_d, dd * sizeof(double), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(bfd.data(), bfd_d, dd * n * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  for (size_t i = 0; i < dd; ++i)
+    for (size_t j = i + 1; j < dd; ++j)
+      mut[i * dd + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
+  if (target)
+  {  // get_gscoords (svpcvp.cpp:494-515), the loops of cvp_prepare_kernel in its operand order
+    for (size_t i = 0; i < dd; ++i)
+    {
+      double acc = 0.0;
+      for (size_t j = 0; j < n; ++j)
+        acc = acc + (double)target[j] * bfd[i * n + j];
+      for (size_t j = 0; j < i; ++j)
+        acc = acc - mu[i * dd + j] * tc[j];
+      tc[i] = acc;
+    }
+    for (size_t i = 0; i < dd; ++i)
+      tc[i] = tc[i] / rd[i];
+  }
+  const double radius = (double)bound_sq + (double)bound_sq * 0x1p-30;
+  std::vector<uint64_t> nodes(dd + 1);
+  std::vector<double> ld, lx;
+  uint64_t icap = std::max<uint64_t>(cap, 4096), found = 0;
+  for (int attempt = 0;; ++attempt)
+  {  // (the count is exact whatever the capacity: a list that did not fit is enumerated once more, with room for it)
+    ld.resize((size_t)icap);
+    lx.resize((size_t)icap * dd);
+    const int rc = fphip_enum_list(ectx, d, radius, mut.data(), rd.data(), nullptr, target ? tc.data() : nullptr, icap,
+                                   ld.data(), lx.data(), &found, nodes.data(), nullptr);
+    if (rc != FPHIP_OK)
+    {
+      if (ectx != g->ctx)
+        snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_list_vectors: enumeration: %s", fphip_last_error(ectx));
+      return rc;
+    }
+    if (found <= icap)
+      break;
+    if (attempt > 0)
+      return gfail_msg(g->ctx, "fphip_list_vectors: the list changed its length between two enumerations");
+    icap = found;
+  }
+  if (found == 0)
+    return FPHIP_OK;
+  std::vector<int64_t> rc_coef((size_t)found * dd), rvec((size_t)found * n), rnorm((size_t)found);
+  std::vector<int> rst((size_t)found);
+  for (size_t i = 0; i < (size_t)found * dd; ++i)
+  {
+    if (!(std::fabs(lx[i]) < 9223372036854775808.0))
+      return gfail_msg(g->ctx, "fphip_list_vectors: a coefficient beyond the int64 range");
+    rc_coef[i] = (int64_t)lx[i];
+  }
+  if (int rc = list_vectors_run(g, lattice, found, rc_coef.data(), target, rvec.data(), rnorm.data(), rst.data()))
+    return rc;
+  // the filter on the exact norm, then (norm, canonical coefficient order: from level d - 1 down)
+  std::vector<size_t> keep;
+  for (size_t i = 0; i < (size_t)found; ++i)
+  {
+    if (rst[i] != 1)
+    {
+      snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_list_vectors: a vector within the radius leaves the int64 range");
+      return FPHIP_UNSUPPORTED;
+    }
+    if (rnorm[i] <= bound_sq)
+      keep.push_back(i);
+  }
+  std::sort(keep.begin(), keep.end(), [&](size_t a, size_t b) {
+    if (rnorm[a] != rnorm[b])
+      return rnorm[a] < rnorm[b];
+    for (size_t k = dd; k-- > 0;)
+      if (rc_coef[a * dd + k] != rc_coef[b * dd + k])
+        return rc_coef[a * dd + k] < rc_coef[b * dd + k];
+    return a < b;
+  });
+  *count = keep.size();
+  for (size_t o = 0; o < keep.size() && o < (size_t)cap; ++o)
+  {
+    memcpy(coef + o * dd, &rc_coef[keep[o] * dd], dd * sizeof(int64_t));
+    memcpy(vec + o * n, &rvec[keep[o] * n], n * sizeof(int64_t));
+    norm[o] = rnorm[keep[o]];
+  }
   return FPHIP_OK;
 }
 

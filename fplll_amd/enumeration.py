@@ -208,3 +208,76 @@ def closest_vector_block(ctx, mut, rdiag, target, maxdist, pruning=None):
     if ev.empty():
         return None
     return ev.solutions[0]
+
+
+class ListResult:
+    """What ``list_block`` returns: ``count`` (exact, may exceed the capacity), ``dist`` (float64[m]) and ``x``
+    (float64[m, d]) of the m = min(count, cap) records present, in canonical order, ``nodes`` (per level, the rule of
+    ``enumerate_block``) and ``stats``."""
+
+    def __init__(self, count, dist, x, nodes, stats):
+        self.count = count
+        self.dist = dist
+        self.x = x
+        self.nodes = nodes
+        self.total_nodes = int(sum(int(v) for v in nodes))
+        self.stats = stats
+
+    def __iter__(self):  # count, dist, x, nodes, stats = list_block(...)
+        return iter((self.count, self.dist, self.x, self.nodes, self.stats))
+
+
+def list_block(ctx, mut, rdiag, pruning, radius, target=None, cap=1 << 20, shard_index=0, shard_count=1):
+    """Every candidate within the fixed squared radius ``radius`` (normalised like rdiag), kept on the GPU during the
+    walk and returned sorted by (distance, coefficients from the top level down): ``fphip_enum_list``.  Without a
+    ``target`` the half tree around the origin (one of each +-x, no zero vector); with one (d float64s, as for
+    ``enumerate_block``) every x around it, distance 0 included.  ``cap`` is the room for records: ``count`` stays exact
+    beyond it, and which ``cap`` records are present is then unspecified; ``cap=0`` only counts.  Blocks above 64 rows
+    and several ranks are declined (``Unsupported``)."""
+    mut = np.ascontiguousarray(mut, dtype=np.float64)
+    d = int(round(mut.size**0.5)) if mut.ndim == 1 else mut.shape[0]
+    if d < 1 or mut.size != d * d:
+        raise ValueError("mut: expected a square matrix, got %d entries" % mut.size)
+    mut = mut.reshape(d, d)
+    rdiag = np.ascontiguousarray(rdiag, dtype=np.float64)
+    if rdiag.shape != (d,):
+        raise ValueError("rdiag: expected %d entries, got shape %r" % (d, rdiag.shape))
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError("cap: a capacity cannot be negative")
+    if not float(radius) >= 0.0:
+        raise ValueError("radius: expected a squared radius >= 0, got %r" % (radius,))
+    pr_ptr = None
+    if pruning is not None and len(pruning):
+        pruning = np.ascontiguousarray(pruning, dtype=np.float64)
+        if pruning.shape != (d,):
+            raise ValueError("pruning: expected %d coefficients, got shape %r" % (d, pruning.shape))
+        pr_ptr = pruning.ctypes.data_as(ctypes.c_void_p)
+    tg_ptr = None
+    if target is not None:
+        target = np.ascontiguousarray(target, dtype=np.float64)
+        if target.shape != (d,):
+            raise ValueError("target: expected %d coordinates, got shape %r" % (d, target.shape))
+        tg_ptr = target.ctypes.data_as(ctypes.c_void_p)
+    if shard_count != 1 or shard_index != 0:
+        raise Unsupported("list enumeration: not with several ranks (shard_count = %d)" % shard_count)
+    lib = ctx.lib
+    lib.fphip_enum_list.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(_lib.EnumStats)]
+    lib.fphip_enum_list.restype = ctypes.c_int
+    dist = np.zeros(cap, dtype=np.float64)
+    x = np.zeros((cap, d), dtype=np.float64)
+    count = ctypes.c_uint64(0)
+    nodes = np.zeros(d + 1, dtype=np.uint64)
+    stats = _lib.EnumStats()
+    rc = lib.fphip_enum_list(ctx.handle, d, ctypes.c_double(radius), mut.ctypes.data_as(ctypes.c_void_p),
+                             rdiag.ctypes.data_as(ctypes.c_void_p), pr_ptr, tg_ptr, cap,
+                             dist.ctypes.data_as(ctypes.c_void_p), x.ctypes.data_as(ctypes.c_void_p),
+                             ctypes.byref(count), nodes.ctypes.data_as(ctypes.c_void_p), ctypes.byref(stats))
+    if rc == _lib.FPHIP_UNSUPPORTED:
+        raise Unsupported("instance declined by the device layer (d=%d): %s" % (d, ctx.last_error()))
+    if rc != _lib.FPHIP_OK:
+        raise _lib.HipError("fphip_enum_list failed: %s" % ctx.last_error())
+    m = min(int(count.value), cap)
+    return ListResult(int(count.value), dist[:m], x[:m], nodes, stats)

@@ -624,6 +624,60 @@ class MatGSOBatch:
         self._chk(rc, "closest_vector")
         return sol, dist, st
 
+    def records_to_vectors(self, coef, target=None, lattice=0):
+        """fphip_list_records_to_vectors: for every row of ``coef`` (int64 [m][d]) the vector sum_i coef_i b_i (minus
+        the int64 ``target`` [n] when given) and its exact squared norm.  Returns (vec int64 [m][n], norm int64 [m],
+        status int32 [m]: 1 ok, -2 beyond 63 bits — that record's outputs are zero)."""
+        c = np.ascontiguousarray(coef, dtype=np.int64)
+        if c.ndim != 2 or c.shape[1] != self.d or c.shape[0] < 1:
+            raise ValueError("records_to_vectors: coef is [m][%d] with m >= 1, got shape %r" % (self.d, c.shape))
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, dtype=np.int64)
+            if t.shape != (self.n,):
+                raise ValueError("records_to_vectors: target is [%d], got shape %r" % (self.n, t.shape))
+        m = c.shape[0]
+        vec = np.zeros((m, self.n), dtype=np.int64)
+        norm = np.zeros(m, dtype=np.int64)
+        st = np.zeros(m, dtype=np.int32)
+        fn = self.lib.fphip_list_records_to_vectors
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64] + [ctypes.c_void_p] * 5
+        self._chk(fn(self.h, lattice, m, c.ctypes.data_as(ctypes.c_void_p),
+                     None if t is None else t.ctypes.data_as(ctypes.c_void_p), vec.ctypes.data_as(ctypes.c_void_p),
+                     norm.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p)), "records_to_vectors")
+        return vec, norm, st
+
+    def list_vectors(self, bound_sq, target=None, cap=1 << 18, ectx=None, lattice=0):
+        """fphip_list_vectors: every lattice vector v with |v - target|^2 <= bound_sq, exactly (target None: around the
+        origin, one of each pair +-v, no zero vector).  Returns (count, coef int64 [m][d], vec int64 [m][n], norm int64
+        [m]) with m = min(count, cap), sorted by (norm, coefficients from the last row down)."""
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, dtype=np.int64)
+            if t.shape != (self.n,):
+                raise ValueError("list_vectors: target is [%d], got shape %r" % (self.n, t.shape))
+        cap = int(cap)
+        if cap < 0 or int(bound_sq) < 0:
+            raise ValueError("list_vectors: cap and bound_sq cannot be negative")
+        coef = np.zeros((cap, self.d), dtype=np.int64)
+        vec = np.zeros((cap, self.n), dtype=np.int64)
+        norm = np.zeros(cap, dtype=np.int64)
+        count = ctypes.c_uint64(0)
+        fn = self.lib.fphip_list_vectors
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        rc = fn(self.h, None if ectx is None else ectx.handle, lattice, None if t is None else t.ctypes.data_as(ctypes.c_void_p),
+                int(bound_sq), cap, coef.ctypes.data_as(ctypes.c_void_p), vec.ctypes.data_as(ctypes.c_void_p),
+                norm.ctypes.data_as(ctypes.c_void_p), ctypes.byref(count))
+        if rc == _lib.FPHIP_UNSUPPORTED:
+            from .enumeration import Unsupported
+            raise Unsupported("list_vectors declined by the device layer (d=%d): %s" % (self.d, self.ctx.last_error()))
+        self._chk(rc, "list_vectors")
+        m = min(int(count.value), cap)
+        return int(count.value), coef[:m], vec[:m], norm[:m]
+
     @property
     def last_kernel_ms(self):
         return float(self.lib.fphip_gso_last_kernel_ms(self.h))

@@ -1,0 +1,72 @@
+"""Lists of short and near lattice vectors: every vector within a radius, exactly.
+
+What the reference does with a BEST_N evaluator that never fills (``FastEvaluator(999999)`` in its test_list_cvp; the
+list behind ``shortest_vectors(..., max_sols)``): kissing numbers, theta series, list decoding.  Everything is computed
+on the GPU behind ``fphip_list_vectors`` (include/fplll_hip.h): update_gso, a list enumeration that keeps every
+candidate on the device (``fphip_enum_list``), the vector kernel (exact int64 vectors and norms) and the filter on the
+exact integer norm; nothing here enumerates on the CPU.  Bases of at most 64 rows with int64 entries, one rank.
+"""
+import numpy as np
+
+from . import _lib
+from .gso import MatGSOBatch, lll_reduction
+
+RED_SUCCESS = 1
+DEFAULT_CAP = 1 << 18
+
+
+def _basis(b, what):
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    if b.ndim != 2 or b.shape[0] < 1 or b.shape[0] > b.shape[1]:
+        raise ValueError("%s: b is [d][n] with 1 <= d <= n, got shape %r" % (what, b.shape))
+    return b
+
+
+def _list(ctx, b, target, bound_sq, reduce, cap, ectx, what):
+    if int(bound_sq) != bound_sq or bound_sq < 0:
+        raise ValueError("%s: bound_sq is a non-negative integer (the squared norms of an integer lattice are)" % what)
+    if int(cap) < 0:
+        raise ValueError("%s: cap cannot be negative" % what)
+    u = None
+    if reduce:
+        b, u, status, _ = lll_reduction(ctx, b, with_u=True)
+        if status != RED_SUCCESS:
+            raise _lib.HipError("%s: lll_reduction ended with status %d" % (what, status))
+    g = MatGSOBatch(ctx, 1, b.shape[0], b.shape[1])
+    try:
+        g.set_basis(b)
+        count, coef, vec, norm = g.list_vectors(int(bound_sq), target=target, cap=int(cap), ectx=ectx)
+    finally:
+        g.close()
+    if u is not None:  # v = coef (u b_in): the coefficients in the caller's basis, exact
+        coef = coef.astype(object).dot(np.asarray(u).astype(object))
+    return count, coef, vec, norm
+
+
+def short_vectors(ctx, b, bound_sq, reduce=True, cap=DEFAULT_CAP, ectx=None):
+    """Every non-zero vector v of the lattice spanned by the rows of ``b`` (int64 [d][n]) with |v|^2 <= bound_sq, one of
+    each pair +-v.  ``reduce=True`` runs ``lll_reduction`` first (the enumeration expects a reduced basis) and expresses
+    the coefficients in the caller's basis through u.  Returns ``(count, coef [m][d], vec [m][n], norm [m])`` with
+    m = min(count, cap): ``count`` is exact whatever ``cap`` is; the rows come sorted by norm."""
+    return _list(ctx, _basis(b, "short_vectors"), None, bound_sq, reduce, cap, ectx, "short_vectors")
+
+
+def vectors_near(ctx, b, target, bound_sq, reduce=True, cap=DEFAULT_CAP, ectx=None):
+    """Every lattice vector w with |w - target|^2 <= bound_sq (``target`` int64 [n]; a target in the lattice is found at
+    norm 0).  Returns ``(count, coef, vec, norm)`` like ``short_vectors``; ``vec`` holds w - target, so the lattice
+    vectors themselves are ``vec + target``."""
+    b = _basis(b, "vectors_near")
+    t = np.ascontiguousarray(target, dtype=np.int64)
+    if t.shape != (b.shape[1],):
+        raise ValueError("vectors_near: target is [%d], got shape %r" % (b.shape[1], t.shape))
+    return _list(ctx, b, t, bound_sq, reduce, cap, ectx, "vectors_near")
+
+
+def theta_series(ctx, b, bound_sq, reduce=True, ectx=None):
+    """``{norm: number of lattice vectors of that squared norm}`` for the norms 0 < norm <= bound_sq, both signs
+    counted (a kissing number is the entry of the minimum)."""
+    count, _, _, norm = short_vectors(ctx, b, bound_sq, reduce=reduce, cap=DEFAULT_CAP, ectx=ectx)
+    if count > len(norm):
+        count, _, _, norm = short_vectors(ctx, b, bound_sq, reduce=reduce, cap=count, ectx=ectx)
+    vals, cnts = np.unique(norm, return_counts=True)
+    return {int(v): 2 * int(c) for v, c in zip(vals, cnts)}

@@ -196,6 +196,36 @@ int fphip_enum_run(fphip_ctx *ctx, int dim, double maxdist, const double *mut, c
  * found on one GPU to the contexts of the others with it, between the collective exchange points. */
 int fphip_enum_lower_bound(fphip_ctx *ctx, double bound);
 
+/*
+ * List mode (ABI version 5): EVERY candidate within a fixed radius, kept on the device during the walk — what the
+ * reference does with a BEST_N evaluator that never fills (FastEvaluator(999999) in its test_list_cvp; the list behind
+ * shortest_vectors(..., max_sols)).  The tree, the per-level counts (nodes_out[0..dim], with the compensation of
+ * fphip_enum_run for a call without / with a target) and every record's distance and coefficients are those of
+ * fphip_enum_run under a callback that returns the bound unchanged, bit for bit; only the way a candidate leaves the
+ * device differs: no callback, no pinned-memory round trip per candidate.
+ *   radius  : the squared radius (normalised like rdiag); it never moves.  fphip_enum_lower_bound is ignored during
+ *             the call.
+ *   target  : NULL: the half tree around the origin (one of each +-x, the zero vector absent); non-NULL: dim doubles
+ *             as for fphip_enum_opts::target (every x around the target, distance exactly 0 included).
+ *   cap     : room of dist[cap] and x[cap][dim] (row-major: x[i * dim + k] = coefficient of level k of record i).
+ *   *count  : the EXACT number of candidates, whatever cap is.  The first min(*count, cap) entries of dist / x are
+ *             written, sorted by (distance ascending, then the coefficients compared from level dim - 1 down to 0):
+ *             with *count <= cap the output is the same from run to run.  With *count > cap the records present are
+ *             SOME cap of the list (which ones is unspecified and may change from run to run), sorted among
+ *             themselves.  cap == 0 is a pure count (dist and x may be NULL).
+ *   stats   : nullable; solutions = candidates = *count.
+ * v1 limits: dim > 64 is declined with FPHIP_UNSUPPORTED and a fphip_last_error text before anything is launched (the
+ * top walk is not compiled for the mode); one rank only (the function has no sharding parameters); no dual, no
+ * sub-solutions, no reference-order mode.
+ */
+int fphip_enum_list(fphip_ctx *ctx, int dim, double radius, const double *mut, const double *rdiag,
+                    const double *pruning, const double *target, uint64_t cap, double *dist, double *x,
+                    uint64_t *count, uint64_t *nodes_out, fphip_enum_stats *stats);
+/* The canonical order of fphip_enum_list applied to n records on the host (no device needed): inputs in any order,
+ * outputs sorted; the output arrays must not overlap the inputs. */
+void fphip_list_sort_records(int dim, uint64_t n, const double *dist_in, const double *x_in, double *dist_out,
+                             double *x_out);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Batched, device-resident Gram-Schmidt + size reduction                                       */
 /*   MatGSO<Z_NR<long>, FP_NR<double>> with GSO_ROW_EXPO (the BKZ fast path, bkz.cpp:816-829),  */
@@ -577,6 +607,28 @@ int fphip_gso_babai(fphip_gso *g, int lattice, int T, const double *v, int start
                     int *status);
 int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets, int method,
                          int64_t *sol_coord, double *dist, int *status);
+
+/*
+ * Lists of short / near vectors (ABI version 5).  fphip_list_vectors: the EXACT set of lattice
+ * vectors v of one lattice with |v - target|^2 <= bound_sq (target NULL: around the origin, one of each pair +-v and no
+ * zero vector), on an LLL-reduced basis of int64 entries, at most 64 rows (more: FPHIP_UNSUPPORTED), one rank.  It runs
+ * update_gso; the true mu and r; with a target its Gram-Schmidt coordinates as fphip_cvp_prepare computes them (no
+ * Babai reduction: the radius is the caller's); fphip_enum_list on `ectx` (NULL: g's context) at radius
+ * bound_sq (1 + 2^-30); the vector kernel (v = sum coef_i b_i - target and |v|^2 in int64 with overflow detection); and
+ * the filter norm <= bound_sq on those exact integers — what decides a vector whose norm EQUALS the bound.  The 2^-30
+ * is the margin of fphip_closest_vector: a heuristic allowance for the rounding of the enumeration's doubles, not a
+ * proved error bound (the reference enlarges its radius by get_max_error_aux there).
+ *   *count : the exact number of such vectors, whatever cap is; the first min(*count, cap) are written — coef [cap][d]
+ *            (coefficients in the basis), vec [cap][n] (v, the target subtracted), norm [cap] — sorted by (norm, then
+ *            the coefficients compared from row d - 1 down to 0).  cap == 0 counts (the arrays may be NULL).
+ * A vector within the radius that leaves the int64 range: FPHIP_UNSUPPORTED with a text.
+ * fphip_list_records_to_vectors is the vector kernel alone over m records of coefficients: vec [m][n], norm [m],
+ * status [m] (1 ok; -2 a value left the 63-bit range: that record's outputs are zero).
+ */
+int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, const int64_t *target, int64_t bound_sq, uint64_t cap,
+                       int64_t *coef, int64_t *vec, int64_t *norm, uint64_t *count);
+int fphip_list_records_to_vectors(fphip_gso *g, int lattice, uint64_t m, const int64_t *coef, const int64_t *target,
+                                  int64_t *vec, int64_t *norm, int *status);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Batched Householder R-factor: MatHouseholder<Z_NR<long>, FP_NR<double>> (householder.h:38)    */
