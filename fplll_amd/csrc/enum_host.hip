@@ -50,6 +50,12 @@ __global__ void enum_walk4_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf 
                                   unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
                                   unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
                                   const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
+// the fifth generation (enum_walk5.hip: child distances straight from the vector test)
+template <bool MU_LDS, bool DUAL>
+__global__ void enum_walk5_kernel(DevShared *g, HostCtl *h, TaskBuf in, TaskBuf out, int d, int Lmax, unsigned task_lo,
+                                  unsigned task_hi, const unsigned *idxlist, int launch_idx, int count_nodes,
+                                  unsigned budget, const double *xhi_root, double *gstk, int Tsplit, unsigned *qh,
+                                  const unsigned *rcnt, unsigned rcap, unsigned long long bound_init);
 // closest-vector mode (fphip_enum_opts::target): the same kernel texts compiled with the zero chain switched off and
 // the zero leaf reported (enum_kernel_cvp.hip, enum_walk_cvp.hip)
 template <bool MU_LDS, bool SUBS, bool DUAL>
@@ -1227,6 +1233,7 @@ restart:
   const bool walk2    = env_int("FPHIP_WALK2", 1) != 0;
   const bool walk3    = env_int("FPHIP_WALK3", 1) != 0;
   const bool walk4    = env_int("FPHIP_WALK4", 1) != 0;
+  const bool walk5    = env_int("FPHIP_WALK5", 1) != 0;
   uint64_t nsol       = 0;
   double kernel_ms    = top_ms, final_ms = 0.0;
   int launches        = 0;
@@ -1644,7 +1651,9 @@ restart:
         // the next sibling is one scalar search (enum_walk_kernel<.., CHAIN = true>, enum_walk.hip); FPHIP_WALK3=0
         // keeps the second generation (<.., false>), FPHIP_WALK2=0 enum_phase_kernel (the A/B partners).  Shortest-vector
         // calls run the fourth generation on top of the third (enum_walk4_kernel, enum_walk4.hip: the second child of
-        // a two-child node ready at the descent); FPHIP_WALK4=0 launches the third
+        // a two-child node ready at the descent), in its fifth-generation form (enum_walk5_kernel, enum_walk5.hip: the
+        // children's distances taken from the lanes of the vector test); FPHIP_WALK5=0 launches the fourth, FPHIP_WALK4=0
+        // the third
 #define FPHIP_LAUNCH2_K(M, D, C) FPHIP_LAUNCH2_KK(enum_walk_kernel, M, D, C)
 #define FPHIP_LAUNCH2_KK(KERNEL, M, D, C)                                                            \
   hipLaunchKernelGGL((KERNEL<M, D, C>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
@@ -1655,7 +1664,13 @@ restart:
 #define FPHIP_LAUNCH2(M, D)                                                                          \
   do                                                                                                 \
   {                                                                                                  \
-    if (walk3 && walk4)                                                                              \
+    if (walk3 && walk4 && walk5)                                                                     \
+      hipLaunchKernelGGL((enum_walk5_kernel<M, D>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
+                         ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,       \
+                         count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0], \
+                         (regioned && !shard_now && !order_now) ? &ctx->qm->fin[0] : (const unsigned *)nullptr, ctx->cap / FPHIP_NQ, \
+                         (unsigned long long)__atomic_load_n(&ctx->h->bound_bits, __ATOMIC_ACQUIRE)); \
+    else if (walk3 && walk4)                                                                         \
       hipLaunchKernelGGL((enum_walk4_kernel<M, D>), dim3(grid), dim3(wpb * 64), lds, ctx->stream, ctx->g, \
                          ctx->h, ctx->buf[cur], ctx->buf[nxt], d, L, lo, hi, idxl, launch_idx,       \
                          count_nodes, bud, ctx->xhi_root, ctx->gstk, Ts, &ctx->qm->head[launch_idx][0], \

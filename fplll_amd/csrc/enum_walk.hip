@@ -9,9 +9,9 @@
 // (enumerate.cpp:218-239).  Same visit set, same arithmetic per node (separate multiply / add, the reference's
 // operand order), same per-level counts and candidates as enum_phase_kernel (enum_kernel.hip) — which stays the
 // kernel of the split launches, of sub-solution calls and the A/B partner of these (FPHIP_WALK2=0).  The final walk
-// launches of shortest-vector calls run the fourth generation (this text a third time, under FPHIP_WALK4: see
-// enum_walk4.hip and the macros below), closest-vector calls and FPHIP_WALK4=0 the third; FPHIP_WALK3=0 selects the
-// second, its A/B partner.
+// launches of shortest-vector calls run the fifth generation (this text once more, under FPHIP_WALK5: see enum_walk5.hip
+// and the macros below), FPHIP_WALK5=0 the fourth (under FPHIP_WALK4: enum_walk4.hip), closest-vector calls and
+// FPHIP_WALK4=0 the third; FPHIP_WALK3=0 selects the second, its A/B partner.
 //
 // The second generation: what changed, and why.  enum_phase_kernel visits the children of a node one test at a
 // time: the first child in its CHILD chain, every later sibling in its STEP loop, and every node's sibling sequence
@@ -115,6 +115,26 @@
 // see the header there): the third with ready pair siblings.  Every line of it sits behind the preprocessor
 // (FPHIP_W4_PAIR): without the macro the text, and with it the machine code of the kernels above, is what it was
 // (tests/perf/walk_isa_diff.py).
+// The fifth generation (enum_walk5.hip compiles this text with FPHIP_WALK5 = 1 into enum_walk5_kernel<MU_LDS, DUAL>, see
+// the header there): the fourth — FPHIP_WALK5 switches FPHIP_WALK4 on — with the pair sibling's distance taken from the
+// lanes of the vector test (FPHIP_W5_PAIR) and the EXPAND loop rotated (FPHIP_W5_AHEAD); either can be switched off
+// on the compiler's command line, which is how each was measured alone.  Every line of it sits behind the preprocessor
+// as well.
+#ifndef FPHIP_WALK5
+#define FPHIP_WALK5 0
+#endif
+#if FPHIP_WALK5
+#define FPHIP_WALK4 1
+#ifndef FPHIP_W5_PAIR
+#define FPHIP_W5_PAIR 1
+#endif
+#ifndef FPHIP_W5_AHEAD
+#define FPHIP_W5_AHEAD 1
+#endif
+#else
+#define FPHIP_W5_PAIR 0
+#define FPHIP_W5_AHEAD 0
+#endif
 #ifndef FPHIP_WALK4
 #define FPHIP_WALK4 0
 #endif
@@ -124,6 +144,10 @@
 #define FPHIP_W4_PAIR 1
 #else
 #define FPHIP_W4_PAIR 0
+#endif
+#if FPHIP_WALK5
+#undef FPHIP_WALK_KERNEL
+#define FPHIP_WALK_KERNEL enum_walk5_kernel
 #endif
 
 namespace fphip
@@ -217,7 +241,15 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
   // z_j of this lane's candidate of an expansion (first step up): 0 in lane 0 of every 16-lane row (lanes 0, 16,
   // 32, 48), +1, -1, +2, -2, ... +30, -30 over the other 60 lanes — 61 distinct candidates, z = 0 four times, so that
   // the first child's distance reaches every lane by one row broadcast (row_bcast0_f64)
+#if FPHIP_W5_PAIR
+  // (the fifth generation: z = 0, +1, -1 in lanes 0, 1, 2 of EVERY row — the distance of either neighbour of x_0
+  //  reaches every lane by one row broadcast as well — and +-2 ... +-27 over the other 52 lanes: 55 distinct candidates,
+  //  the three nearest four times each; FPHIP_ZONCE masks the copies out of a ballot)
+  double zz = (double)zig_of((lane & 15) < 3 ? (lane & 15) : (lane & 15) + 13 * (lane >> 4), false);
+#define FPHIP_ZONCE 0xfff8fff8fff8ffffull
+#else
   double zz = (lane & 15) == 0 ? 0.0 : (double)zig_of(lane - (lane >> 4), false);
+#endif
   FPHIP_IN_VGPR(zz);
 
   unsigned long long mbits =
@@ -559,8 +591,37 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
           // ================= EXPAND chain: all children of the node at level k, descend into the first ====
           // (state: a counted node at level k with column S = S_k, distance nd; ka = 4 k)
           kc = k - 1;
+#if FPHIP_W5_AHEAD
+          // The loop rotated: what a level's test needs from memory and from the crossbar — the centre's broadcast, the
+          // (r, pruning) pair, the mu row — is asked for where the level is entered, at the end of the descent above it
+          // (FPHIP_NEXT_LEVEL) and here for the first one, not at the top of the level's own iteration.  A descent forms
+          // the child's column first and asks at once, so that its bookkeeping (the count, the distance's broadcast,
+          // the masks) runs while the answers travel.  Same instructions, same operands: another order.
+          v4i q1;
+          int kb = ka;  // (the address operand of the broadcasts: 4 * the level asked for)
+#define FPHIP_NEXT_LEVEL()                                           \
+  do                                                                 \
+  {                                                                  \
+    asm volatile("" : "+s"(kc));                                     \
+    kb -= 4;                                                         \
+    asm("" : "+v"(kb)); /* (one address register, not two) */        \
+    c1 = bp_f64(S, kb);                                              \
+    q1 = rp_issue2(rptab, (unsigned)kc * MUROW8);                    \
+    if constexpr (MU_LDS)                                            \
+      mk1 = ld_off(mu_s, tri8(kc) + min(lane8, ((unsigned)kc << 3) - 8u)); \
+    else                                                             \
+      mk1 = ld_row(mu_b, (unsigned)kc * MUROW8, lane8);              \
+  } while (0)
+          FPHIP_NEXT_LEVEL();
+#else
+#define FPHIP_NEXT_LEVEL() \
+  do                       \
+  {                        \
+  } while (0)
+#endif
           for (;;)
           {
+#if !FPHIP_W5_AHEAD
             asm volatile("" : "+s"(kc));
             const unsigned kc8 = (unsigned)kc << 3;
             v4i q1             = rp_issue2(rptab, (unsigned)kc * MUROW8);
@@ -570,6 +631,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               mk1 = ld_row(mu_b, (unsigned)kc * MUROW8, lane8);
             ka -= 4;
             c1 = bp_f64(S, ka);  // center[kk-1]
+#endif
             // x_0 = rint(c) here, not roundto(c): on a tie (a1 = +-0.5 exactly) the two nearest integers give the same
             // multiset of |a1 + z_j| over the 61 candidates — {0.5, 0.5, 1.5, 1.5, ... 29.5, 29.5, 30.5} — so the
             // ballot's popcount and the distance of z = 0 are those of roundto's x_0 (tests/test_walk_tie_model.py),
@@ -617,13 +679,70 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             if (CHAIN && c == 4)
             {  // a link of a chain: level kc has no sibling to come back to — nothing of it is stored
               B &= ~me;
+#if FPHIP_W5_AHEAD
+              // the column first, and the next centre's broadcast at once: the count, the distance and the next
+              // header's loads run while the crossbar works
+              S = S - (DUAL ? a1 : x1) * mk1;
+              --kc;
+              FPHIP_NEXT_LEVEL();
+              cnt32 = add_bit(me, cnt32);
+              nd    = row_bcast0_f64(ndj);
+#else
               cnt32 = add_bit(me, cnt32);
               nd    = row_bcast0_f64(ndj);  // the child's distance: ndj of z = 0, lane 0 of every row
               S     = S - (DUAL ? a1 : x1) * mk1;
               --kc;
+#endif
               continue;
             }
+#if FPHIP_W5_PAIR
+            // (the tie test once, for the pair and for the correction below)
+            unsigned long long tie = __builtin_amdgcn_ballot_w64(fabs(a1) == 0.5);
+            asm("" : "+s"(tie));
+            if (c == 8)
+            {
+              if (tie != 0ull)
+              {  // a tie pair: both neighbours share a distance, the direction is roundto's — the fourth generation's
+                 // computation, below
+                FPHIP_EXIT();
+              }
+              else
+              {  // exactly two children (z = 0 and one neighbour, four lanes each) and no tie: the sibling is the
+                 // test's own candidate z = +1 (bit 1 of the ballot: c > x_0, the direction STEP takes) or z = -1
+                 // (bit 2).  Its distance is ndj of that lane — (a1 + z) and (x_0 + z) - c are the same double, the rest
+                 // is STEP's own sequence (tests/test_walk5_model_cpu.py) —, its coefficient x_0 + z.  Stored as the
+                 // fourth generation stores it.
+                double x2, nd2;
+                if ((m & 2ull) != 0ull)
+                {
+                  x2  = x1 + 1.0;
+                  nd2 = row_bcast_f64<1>(ndj);
+                }
+                else
+                {
+                  x2  = x1 - 1.0;
+                  nd2 = row_bcast_f64<2>(ndj);
+                }
+                const double S1 = S - (DUAL ? a1 : x1) * mk1;
+                S               = S - (DUAL ? x2 - c1 : x2) * mk1;
+                FPHIP_PUSH(kc < Ts - 1, kc + 1, tri8(kc + 2));
+                P |= me;
+                Q |= me;
+                B &= ~me;
+                x0s   = sel_f64(me, x2, x0s);
+                pds   = sel_f64(me, nd2, pds);
+                cnt32 = add_bit(me, cnt32);
+                S     = S1;
+                --kc;
+                FPHIP_NEXT_LEVEL();
+                nd = row_bcast0_f64(ndj);
+                continue;
+              }
+            }
+            if (tie != 0ull)
+#else
             if (__builtin_amdgcn_ballot_w64(fabs(a1) == 0.5) != 0ull)
+#endif
             {  // roundto(): ties away from zero
               asm volatile("");
               const bool fix = (a1 < 0.0) == (c1 > 0.0);
@@ -632,7 +751,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               a1 = __hiloint2double(__double2hiint(a1) ^ (fix ? (int)0x80000000 : 0), __double2loint(a1));
             }
 #if FPHIP_W4_PAIR
-            if (c == 5)
+            if (c == (FPHIP_W5_PAIR ? 8 : 5))
             {  // exactly two children: the sibling is formed HERE, where its operands are in registers, by the
                // operations, operands and order of STEP (see the header of enum_walk4.hip) — its column goes into the
                // slot of the push, its distance and coefficient into lane kc of pds and x0s; nothing else is kept
@@ -652,6 +771,7 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
               nd    = row_bcast0_f64(ndj);
               S  = S1;
               --kc;
+              FPHIP_NEXT_LEVEL();
               continue;
             }
             Q &= ~me;
@@ -666,14 +786,24 @@ __global__ void __launch_bounds__(FPHIP_MAX_BLOCK) __attribute__((amdgpu_waves_p
             cs    = sel_f64(me, c1, cs);
             x0s   = sel_f64(me, x1, x0s);
             pds   = sel_f64(me, nd, pds);
+#if FPHIP_W5_PAIR
+            st    = wl_i32(__builtin_popcountll(m & FPHIP_ZONCE) << 8, kc, st);
+#else
             st    = wl_i32((c - 3) << 8, kc, st);
+#endif
             cnt32 = add_bit(me, cnt32);
             nd    = row_bcast0_f64(ndj);  // the first child's distance, as in the chain descent
             S     = S - (DUAL ? a1 : x1) * mk1;
             --kc;
+            FPHIP_NEXT_LEVEL();
           }
+#undef FPHIP_NEXT_LEVEL
           k = kc + 1;
+#if FPHIP_W5_AHEAD
+          ka = lane_addr(k);  // (the loop has its own address register)
+#else
           ka += 4;
+#endif
           if (ev != EV_FAIL)
             break;  // EV_SPECIAL
           // no surviving child: the next sibling — CHAIN: at the lowest level that has one; else at level k (at the

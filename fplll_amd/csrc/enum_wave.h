@@ -46,6 +46,24 @@ __device__ __forceinline__ double row_bcast0_f64(double v)
       : "v"(v));
   return r;
 }
+// Lane N (1 or 2) of each row into every lane of that row: row_bcast0_f64 for another lane.
+template <int N>
+__device__ __forceinline__ double row_bcast_f64(double v)
+{
+  static_assert(N == 1 || N == 2, "row_newbcast:1 / :2");
+  double r;
+  if constexpr (N == 1)
+    asm("s_nop 1\n\t"
+        "v_mov_b64_dpp %0, %1 row_newbcast:1 row_mask:0xf bank_mask:0xf"
+        : "=v"(r)
+        : "v"(v));
+  else
+    asm("s_nop 1\n\t"
+        "v_mov_b64_dpp %0, %1 row_newbcast:2 row_mask:0xf bank_mask:0xf"
+        : "=v"(r)
+        : "v"(v));
+  return r;
+}
 // 4 * level in a VGPR: the address operand of the bpermutes of one level
 __device__ __forceinline__ int lane_addr(int level)
 {
