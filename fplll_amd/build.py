@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 
 HIP_SOURCES = ["enum_kernel.hip", "enum_walk.hip", "enum_kernel_cvp.hip", "enum_walk_cvp.hip", "enum_walk4.hip", "enum_walk5.hip", "enum_kernel_list.hip", "enum_walk_list.hip", "enum_kernel_cvp_list.hip", "enum_walk_cvp_list.hip", "enum_deal.hip", "enum_order.hip", "enum_host.hip", "gso_kernel.hip", "gso_sweep2.hip", "lll_kernel.hip", "lll_kernel_early.hip", "hlll_kernel.hip", "hh_blocked.hip", "hh_rows.hip", "hlll_x.hip", "lll_x.hip", "bkz_kernel.hip", "bkzs_kernel.hip", "bkz_kernel_u.hip", "bkzs_kernel_u.hip", "hlll_kernel_u.hip", "hlll_x_u.hip", "lll_x_u.hip", "gso_host.hip", "lll_gram.hip", "gram_host.hip", "cvp_prepare.hip", "list_vectors.hip", "pruner_volume.hip", "pruner_search.hip", "gso_util_host.hip"]
-HIP_HEADERS = ["dev_mem.h", "dev_cache.h", "trace.h", "pruner_tables.h", "pruner_engine.h", "enum_device.h", "enum_order.h", "enum_wave.h", "gso_device.h", "gram_device.h", "gso_wave.h", "gso_sweep2.h", "ftx.h", "lll_wave.h", "lll_stream.h", os.path.join(ROOT, "include", "fplll_hip.h")]
+HIP_HEADERS = ["dev_mem.h", "dev_cache.h", "trace.h", "pruner_tables.h", "pruner_engine.h", "enum_device.h", "enum_order.h", "enum_wave.h", "gso_device.h", "gram_device.h", "gso_wave.h", "gso_sweep2.h", "ftx.h", "lll_wave.h", "lll_stream.h", "kernels.h", "enum_kernels.h", "host_common.h", os.path.join(ROOT, "include", "fplll_hip.h")]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17",
     "-ffp-contract=off",  # fplll's arithmetic is separate mul/add (nr/nr_FP_d.inl:178); no FMA
@@ -118,9 +118,11 @@ def build_hip(force=False):
             jobs.append([hipcc()] + HIPCC_FLAGS + extra + PER_FILE_FLAGS.get(os.path.basename(src), []) +
                         ["-c", "-o", obj, src])
             relink = True
-    if jobs:  # the translation units are independent: compile them side by side
+    if jobs:  # the translation units are independent: compile them side by side — MAX_JOBS of them where that is
+        # set, otherwise at most 16 (a shared machine shows more CPUs than one build may use)
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
+        limit = int(os.environ.get("MAX_JOBS") or 0) or min(16, os.cpu_count() or 1)
+        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), limit))) as ex:
             list(ex.map(_run, jobs))
     if relink:
         _run([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-pthread", "-o", out] + objs)

@@ -39,6 +39,7 @@
 // (fphip_gso_bkz_insert_stats).  The numpy replay in tests/test_bkz_transform_cpu.py is the model.
 
 #include "lll_wave.h"
+#include "kernels.h"
 
 namespace fphip
 {

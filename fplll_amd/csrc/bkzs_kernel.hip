@@ -45,6 +45,7 @@
 // of rerandomize_block.  ustats[5]: insertions by kind (fphip_gso_bkz_insert_stats).
 
 #include "lll_wave.h"
+#include "kernels.h"
 
 namespace fphip
 {

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "gso_device.h"
+#include "kernels.h"
 
 namespace fphip
 {

@@ -66,7 +66,7 @@
 
 #include "enum_device.h"
 #include "enum_wave.h"
-
+#include "enum_kernels.h"
 
 #ifndef FPHIP_CVP
 #define FPHIP_CVP 0

@@ -13,20 +13,11 @@
 
 #include "../../include/fplll_hip.h"
 #include "dev_mem.h"
-#include "gram_device.h"
-#include "gso_device.h"
+#include "host_common.h"
+#include "kernels.h"
 #include "trace.h"
 
-namespace fphip
-{
-template <int NQ> __global__ void lll_gram_kernel(GramBatch P, double delta, double eta, double logdelta, int siegel);
-template <int NQ> __global__ void gram_update_kernel(GramBatch P);
-}  // namespace fphip
 using namespace fphip;
-
-hipStream_t fphip_ctx_stream(fphip_ctx *ctx);
-char *fphip_ctx_errbuf(fphip_ctx *ctx);
-int fphip_ctx_num_cus(fphip_ctx *ctx);
 
 struct fphip_gram
 {
@@ -37,18 +28,7 @@ struct fphip_gram
   int waves_per_block;
 };
 
-static int qfail(fphip_ctx *ctx, const char *what, hipError_t e)
-{
-  snprintf(fphip_ctx_errbuf(ctx), 512, "%s failed: %s", what, hipGetErrorString(e));
-  return FPHIP_ERROR;
-}
-#define QCHK(call)                       \
-  do                                     \
-  {                                      \
-    hipError_t e_ = (call);              \
-    if (e_ != hipSuccess)                \
-      return qfail(h->ctx, #call, e_);   \
-  } while (0)
+#define QCHK(call) CHK(h->ctx, call)
 
 static const size_t kPad = 4096;  // the LDS-DMA ring reads whole 16-byte lanes past the end of a row
 
@@ -275,22 +255,12 @@ static int gram_launch(fphip_gram *h, int which, double delta, double eta, doubl
     grid = cap;
   hipStream_t s = fphip_ctx_stream(h->ctx);
   QCHK(hipEventRecord(h->ev[0], s));
-#define FPHIP_GRAM_LAUNCH(NQ_)                                                                                         \
-  do                                                                                                                   \
-  {                                                                                                                    \
-    if (which == 1)                                                                                                    \
-      hipLaunchKernelGGL(lll_gram_kernel<NQ_>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, eta, logdelta, siegel); \
-    else                                                                                                               \
-      hipLaunchKernelGGL(gram_update_kernel<NQ_>, dim3(grid), dim3(wpb * 64), lds, s, h->P);                           \
-  } while (0)
-  switch (nq)
-  {
-  case 1: FPHIP_GRAM_LAUNCH(1); break;
-  case 2: FPHIP_GRAM_LAUNCH(2); break;
-  case 3: FPHIP_GRAM_LAUNCH(3); break;
-  default: FPHIP_GRAM_LAUNCH(4); break;
-  }
-#undef FPHIP_GRAM_LAUNCH
+  dispatch_nq(nq, [&](auto NQ) {
+    if (which == 1)
+      hipLaunchKernelGGL(lll_gram_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, eta, logdelta, siegel);
+    else
+      hipLaunchKernelGGL(gram_update_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, h->P);
+  });
   QCHK(hipGetLastError());
   QCHK(hipEventRecord(h->ev[1], s));
   QCHK(hipStreamSynchronize(s));

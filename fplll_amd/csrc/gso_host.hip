@@ -36,99 +36,9 @@ __attribute__((visibility("hidden"))) int prune_block(VolumeEngine *eng, int n, 
                                                       double *coefficients, double *expectation);
 }  // namespace fphip_pruner
 
-#ifndef FPHIP_GSO_RING
-#define FPHIP_GSO_RING 6
-#endif
-
-namespace fphip
-{
-template <int NQ> __global__ void gso_sweep_kernel(GsoBatch P, int kmin, int kend, double eta, int mode);
-template <int NQ>
-__global__ void bkz_kernel(GsoBatch P, int block_size, double delta, double eta, double logdelta,
-                           int use_max_loops, int max_loops, int stack_doubles);
-template <int NQ>
-__global__ void bkzs_kernel(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size,
-                            int top_flags, double delta, double eta, double logdelta, int max_loops,
-                            int stack_doubles);
-namespace sdv
-{
-template <int NQ>
-__global__ void bkzd_kernel(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size,
-                            int top_flags, double delta, double eta, double logdelta, int max_loops,
-                            int stack_doubles, int run_mode);
-}
-// the same three with the transformation matrix u (FPHIP_BKZ_TRANSFORM): bkz_kernel_u.hip, bkzs_kernel_u.hip
-template <int NQ>
-__global__ void bkz_kernel_u(GsoBatch P, int block_size, double delta, double eta, double logdelta,
-                             int use_max_loops, int max_loops, int stack_doubles, unsigned long long *ustats);
-template <int NQ>
-__global__ void bkzs_kernel_u(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size,
-                              int top_flags, double delta, double eta, double logdelta, int max_loops,
-                              int stack_doubles, unsigned long long *ustats);
-namespace sdv
-{
-template <int NQ>
-__global__ void bkzd_kernel_u(GsoBatch P, BkzStrat S, BkzMail *mailbox, int *abort_flag, int block_size,
-                              int top_flags, double delta, double eta, double logdelta, int max_loops,
-                              int stack_doubles, int run_mode, unsigned long long *ustats);
-}
-template <int NQ> __global__ void hlll_kernel(HhBatch P, double delta, double theta, long long iter_cap);
-template <int NQ>
-__global__ void hlll_u_kernel(HhBatch P, double delta, double theta, long long iter_cap, long long *Uall, int ldu);
-template <int NQ> __global__ void hh_blocked_kernel(HhBatch P, double *Tbuf);
-struct HlllX
-{
-  double *Rlo, *Vlo;
-  double *sc;
-  long long *prevE;
-  double delta, theta;
-  long long iter_cap;
-  const int *only_failed;
-  double *Thi, *Tlo;
-  double *Rx, *Vx;
-};
-template <int NQ, class FT> __global__ void hlll_x_kernel(HhBatch P, HlllX X);
-template <int NQ, class FT> __global__ void hlll_x_u_kernel(HhBatch P, HlllX X, long long *Uall, int ldu);
-struct LllX
-{
-  int batch, d, n, ldn, ldd, row_expo;
-  long long *b, *b2;
-  double *bf;
-  double *mu_hi, *mu_lo;
-  double *r_hi, *r_lo;
-  double *gf_hi, *gf_lo;
-  double *mu_x, *r_x, *gf_x;
-  long long *rexp;
-  int *status, *info;
-  const int *only_failed;
-  int kmin, kstart, kend;
-  double delta, eta;
-  int *slot_out;
-};
-template <int NQ, class FT> __global__ void lll_x_kernel(LllX A);
-template <int NQ, class FT> __global__ void lll_x_u_kernel(LllX A, long long *Uall, long long *U2all, int ldu);
-__global__ void dd_op_kernel(const double *ahi, const double *alo, const double *bhi, const double *blo,
-                             double *ohi, double *olo, int op, int count);
-template <class FT> __global__ void ftx_op_kernel(const double *pa, const double *pb, double *po, int op, int count);
-template <int NQ, bool EARLY>
-__global__ void lll_kernel(GsoBatch P, int kmin, int kstart, int kend, double delta, double eta,
-                           double logdelta);
-// cvp_prepare.hip: the closest-vector solver's target preparation and MatGSOInterface::babai, one target per lane
-__global__ void cvp_unscale_kernel(GsoBatch P, int lattice, double *bfd, double *mu, double *rd);
-__global__ void cvp_prepare_kernel(CvpPrep P);
-__global__ void list_vectors_kernel(ListVec P);  // list_vectors.hip
-__global__ void cvp_babai_kernel(int T, int ldt, int d, int start, int dimension, const double *mu, const double *v,
-                                 long long *w, int *status, double *wx);
-}
+#include "host_common.h"
+#include "kernels.h"
 using namespace fphip;
-
-hipStream_t fphip_ctx_stream(fphip_ctx *ctx);
-char *fphip_ctx_errbuf(fphip_ctx *ctx);
-int fphip_ctx_num_cus(fphip_ctx *ctx);
-int fphip_ctx_device(fphip_ctx *ctx);
-int fphip_ctx_ensure_task_buffers(fphip_ctx *ctx);  // enum_host.hip
-int fphip_ctx_set_task_cap(fphip_ctx *ctx, unsigned cap);
-int fphip_ctx_allow_wide_target(fphip_ctx *ctx, int on);  // enum_host.hip: closest-vector calls above 64 rows
 
 struct fphip_gso
 {
@@ -174,23 +84,7 @@ struct fphip_gso
   unsigned long long bkz_stats[5]  = {0, 0, 0, 0, 0};
 };
 
-static int gfail(fphip_ctx *ctx, const char *what, hipError_t e)
-{
-  snprintf(fphip_ctx_errbuf(ctx), 512, "%s failed: %s", what, hipGetErrorString(e));
-  return FPHIP_ERROR;
-}
-static int gfail_msg(fphip_ctx *ctx, const char *msg)
-{
-  snprintf(fphip_ctx_errbuf(ctx), 512, "%s", msg);
-  return FPHIP_ERROR;
-}
-#define GCHK(call)                            \
-  do                                          \
-  {                                           \
-    hipError_t e_ = (call);                   \
-    if (e_ != hipSuccess)                     \
-      return gfail(g->ctx, #call, e_);        \
-  } while (0)
+#define GCHK(call) CHK(g->ctx, call)
 
 // (internal hook of fphip_destroy, enum_host.hip: not exported)
 extern "C" __attribute__((visibility("hidden"))) void fphip_gso_release_all(fphip_ctx *ctx) { (void)ctx; }
@@ -479,8 +373,8 @@ static int launch(fphip_gso *g, int kmin, int kend, double eta, int mode, const 
   hipStream_t s = fphip_ctx_stream(g->ctx);
   if (!la && g->sweep_version == 2)
   {  // gso_sweep2_kernel: its own ring geometry (gso_sweep2.h)
-    const int ring   = nq == 1 ? s2::Cfg<1>::RING : nq == 2 ? s2::Cfg<2>::RING : nq == 3 ? s2::Cfg<3>::RING : s2::Cfg<4>::RING;
-    const int wps    = nq == 4 ? s2::Cfg<4>::WAVES_PER_SIMD : nq == 3 ? s2::Cfg<3>::WAVES_PER_SIMD : s2::Cfg<1>::WAVES_PER_SIMD;
+    const int ring   = dispatch_nq(nq, [](auto NQ) { return s2::Cfg<NQ>::RING; });
+    const int wps    = dispatch_nq(nq, [](auto NQ) { return s2::Cfg<NQ>::WAVES_PER_SIMD; });
     const size_t lds2 = (size_t)wpb * ring;
     // NQ = 3: three blocks of four waves per CU, not the four that fit — measured 100.8-101.9 ms against
     // 104.5-105.1 ms at batch 8192 (three alternating repetitions on one box, profiles/r04_gso_roof_ab.log):
@@ -494,21 +388,7 @@ static int launch(fphip_gso *g, int kmin, int kend, double eta, int mode, const 
     if (grid > cap2)
       grid = cap2;
     GCHK(hipEventRecord(g->ev[0], s));
-    switch (nq)
-    {
-    case 1:
-      hipLaunchKernelGGL(s2::gso_sweep2_kernel<1>, dim3(grid), dim3(wpb * 64), lds2, s, g->P, g->muA, g->m16, g->flag16, kmin, kend, eta, mode);
-      break;
-    case 2:
-      hipLaunchKernelGGL(s2::gso_sweep2_kernel<2>, dim3(grid), dim3(wpb * 64), lds2, s, g->P, g->muA, g->m16, g->flag16, kmin, kend, eta, mode);
-      break;
-    case 3:
-      hipLaunchKernelGGL(s2::gso_sweep2_kernel<3>, dim3(grid), dim3(wpb * 64), lds2, s, g->P, g->muA, g->m16, g->flag16, kmin, kend, eta, mode);
-      break;
-    default:
-      hipLaunchKernelGGL(s2::gso_sweep2_kernel<4>, dim3(grid), dim3(wpb * 64), lds2, s, g->P, g->muA, g->m16, g->flag16, kmin, kend, eta, mode);
-      break;
-    }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(s2::gso_sweep2_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds2, s, g->P, g->muA, g->m16, g->flag16, kmin, kend, eta, mode); });
     GCHK(hipGetLastError());
     GCHK(hipEventRecord(g->ev[1], s));
     GCHK(hipStreamSynchronize(s));
@@ -531,43 +411,17 @@ static int launch(fphip_gso *g, int kmin, int kend, double eta, int mode, const 
   }
   GCHK(hipEventRecord(g->ev[0], s));
   if (la)
-  {
-    // (the LLL_EARLY_RED instantiations live in lll_kernel_early.hip)
-#define FPHIP_LLL_LAUNCH(NQ_)                                                                                          \
-  do                                                                                                                   \
-  {                                                                                                                    \
-    if (g->P.lll_early || g->P.u)                                                                                      \
-      hipLaunchKernelGGL((lll_kernel<NQ_, true>), dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, la->kstart, kend,    \
-                         la->delta, eta, la->logdelta);                                                                \
-    else                                                                                                               \
-      hipLaunchKernelGGL((lll_kernel<NQ_, false>), dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, la->kstart, kend,   \
-                         la->delta, eta, la->logdelta);                                                                \
-  } while (0)
-    switch (nq)
-    {
-    case 1: FPHIP_LLL_LAUNCH(1); break;
-    case 2: FPHIP_LLL_LAUNCH(2); break;
-    case 3: FPHIP_LLL_LAUNCH(3); break;
-    default: FPHIP_LLL_LAUNCH(4); break;
-    }
-#undef FPHIP_LLL_LAUNCH
-  }
+    dispatch_nq(nq, [&](auto NQ) {
+      // (the LLL_EARLY_RED instantiations live in lll_kernel_early.hip)
+      if (g->P.lll_early || g->P.u)
+        hipLaunchKernelGGL((lll_kernel<NQ, true>), dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, la->kstart, kend,
+                           la->delta, eta, la->logdelta);
+      else
+        hipLaunchKernelGGL((lll_kernel<NQ, false>), dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, la->kstart, kend,
+                           la->delta, eta, la->logdelta);
+    });
   else
-  switch (nq)
-  {
-  case 1:
-    hipLaunchKernelGGL(gso_sweep_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, kend, eta, mode);
-    break;
-  case 2:
-    hipLaunchKernelGGL(gso_sweep_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, kend, eta, mode);
-    break;
-  case 3:
-    hipLaunchKernelGGL(gso_sweep_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, kend, eta, mode);
-    break;
-  default:
-    hipLaunchKernelGGL(gso_sweep_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, kend, eta, mode);
-    break;
-  }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(gso_sweep_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, kmin, kend, eta, mode); });
   GCHK(hipGetLastError());
   GCHK(hipEventRecord(g->ev[1], s));
   if (g->P.sess_mode != 0)
@@ -742,8 +596,6 @@ extern "C" int fphip_gso_size_reduce(fphip_gso *g, int kappa_min, int kappa_end,
 }
 
 static int ensure_lll_buffers(fphip_gso *g);
-extern "C" int fphip_gso_lll_flags(fphip_gso *g, int kappa_min, int kappa_start, int kappa_end,
-                                   double delta, double eta, int flags, int *status, int *info);
 
 // LLLReduction<Z_NR<long>, FP_NR<double>>(m, delta, eta, LLL_DEFAULT).lll(kappa_min, kappa_start,
 // kappa_end, 0) on a fresh MatGSO(b, GSO_ROW_EXPO) of every lattice (lll.cpp:44-164,
@@ -1114,49 +966,19 @@ static int gso_lll_ex(fphip_gso *g, int kappa_min, int kappa_start, int kappa_en
   {
     long long *u = g->P.u, *u2 = g->P.u2;
     const int ldu = g->P.ldd;
-    if (precision == 212)  // (nq == 1: lll_x_u_covers_quad_double above)
-      hipLaunchKernelGGL((lll_x_u_kernel<1, QD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu);
-    else if (precision == 106)
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL((lll_x_u_kernel<1, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      case 2: hipLaunchKernelGGL((lll_x_u_kernel<2, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      case 3: hipLaunchKernelGGL((lll_x_u_kernel<3, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      default: hipLaunchKernelGGL((lll_x_u_kernel<4, DD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      }
-    else
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL((lll_x_u_kernel<1, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      case 2: hipLaunchKernelGGL((lll_x_u_kernel<2, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      case 3: hipLaunchKernelGGL((lll_x_u_kernel<3, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      default: hipLaunchKernelGGL((lll_x_u_kernel<4, double>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); break;
-      }
+    dispatch_precision(precision, [&](auto ft) {
+      using FT = typename decltype(ft)::type;
+      if constexpr (std::is_same<FT, QD>::value)  // (nq == 1: lll_x_u_covers_quad_double above)
+        hipLaunchKernelGGL((lll_x_u_kernel<1, QD>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu);
+      else
+        dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL((lll_x_u_kernel<NQ, FT>), dim3(grid), dim3(64), 0, s, A, u, u2, ldu); });
+    });
   }
-  else if (precision == 212)
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL((lll_x_kernel<1, QD>), dim3(grid), dim3(64), 0, s, A); break;
-    case 2: hipLaunchKernelGGL((lll_x_kernel<2, QD>), dim3(grid), dim3(64), 0, s, A); break;
-    case 3: hipLaunchKernelGGL((lll_x_kernel<3, QD>), dim3(grid), dim3(64), 0, s, A); break;
-    default: hipLaunchKernelGGL((lll_x_kernel<4, QD>), dim3(grid), dim3(64), 0, s, A); break;
-    }
-  else if (precision == 106)
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL((lll_x_kernel<1, DD>), dim3(grid), dim3(64), 0, s, A); break;
-    case 2: hipLaunchKernelGGL((lll_x_kernel<2, DD>), dim3(grid), dim3(64), 0, s, A); break;
-    case 3: hipLaunchKernelGGL((lll_x_kernel<3, DD>), dim3(grid), dim3(64), 0, s, A); break;
-    default: hipLaunchKernelGGL((lll_x_kernel<4, DD>), dim3(grid), dim3(64), 0, s, A); break;
-    }
   else
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL((lll_x_kernel<1, double>), dim3(grid), dim3(64), 0, s, A); break;
-    case 2: hipLaunchKernelGGL((lll_x_kernel<2, double>), dim3(grid), dim3(64), 0, s, A); break;
-    case 3: hipLaunchKernelGGL((lll_x_kernel<3, double>), dim3(grid), dim3(64), 0, s, A); break;
-    default: hipLaunchKernelGGL((lll_x_kernel<4, double>), dim3(grid), dim3(64), 0, s, A); break;
-    }
+    dispatch_precision(precision, [&](auto ft) {
+      using FT = typename decltype(ft)::type;
+      dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL((lll_x_kernel<NQ, FT>), dim3(grid), dim3(64), 0, s, A); });
+    });
   GCHK(hipGetLastError());
   GCHK(hipEventRecord(g->ev[1], s));
   GCHK(hipStreamSynchronize(s));
@@ -1400,42 +1222,14 @@ static int bkz_launch(fphip_gso *g, int block_size, double delta, double eta, in
   hipStream_t s     = fphip_ctx_stream(g->ctx);
   const double logd = std::log(delta);
   if (lds > 64 * 1024 && g->bkz_u)
-  {
-    switch (nq)
-    {
-    case 1: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 2: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 3: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    default: GCHK(hipFuncSetAttribute((const void *)bkz_kernel_u<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    }
-  }
+    GCHK(dispatch_nq(nq, [&](auto NQ) { return allow_lds(bkz_kernel_u<NQ>, lds); }));
   else if (lds > 64 * 1024)
-  {
-    switch (nq)
-    {
-    case 1: GCHK(hipFuncSetAttribute((const void *)bkz_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 2: GCHK(hipFuncSetAttribute((const void *)bkz_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 3: GCHK(hipFuncSetAttribute((const void *)bkz_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    default: GCHK(hipFuncSetAttribute((const void *)bkz_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    }
-  }
+    GCHK(dispatch_nq(nq, [&](auto NQ) { return allow_lds(bkz_kernel<NQ>, lds); }));
   GCHK(hipEventRecord(g->ev[0], s));
   if (g->bkz_u)
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL(bkz_kernel_u<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
-    case 2: hipLaunchKernelGGL(bkz_kernel_u<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
-    case 3: hipLaunchKernelGGL(bkz_kernel_u<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
-    default: hipLaunchKernelGGL(bkz_kernel_u<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); break;
-    }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(bkz_kernel_u<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles, g->bkz_stats_d); });
   else
-  switch (nq)
-  {
-  case 1: hipLaunchKernelGGL(bkz_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles); break;
-  case 2: hipLaunchKernelGGL(bkz_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles); break;
-  case 3: hipLaunchKernelGGL(bkz_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles); break;
-  default: hipLaunchKernelGGL(bkz_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles); break;
-  }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(bkz_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, block_size, delta, eta, logd, use_loops, max_loops, stack_doubles); });
   GCHK(hipGetLastError());
   GCHK(hipEventRecord(g->ev[1], s));
   GCHK(hipStreamSynchronize(s));
@@ -1542,7 +1336,7 @@ static int dump_gso_output(fphip_gso *g, const TourHooks &hooks, const std::vect
   for (size_t L = 0; L < B; ++L)
     if (st[L] == 1 || st[L] == 7 || st[L] == 8)  // (a failing tour throws past the dump, bkz.cpp:611-614)
       if (dump_gso_entry(g, L, true, "Output", -1, hooks.seconds(), &rdg[L * d], &rex[L * d], rows[L]) != FPHIP_OK)
-        return gfail_msg(g->ctx, "BKZ_DUMP_GSO: cannot write the dump file");
+        return fail_msg(g->ctx, "BKZ_DUMP_GSO: cannot write the dump file");
   return FPHIP_OK;
 }
 
@@ -1584,7 +1378,7 @@ static int auto_abort_loop(fphip_gso *g, int block_size, bool use_loops, int max
       {  // "Input" (bkz.cpp:536-539) / the entry at the end of tour loop - 1 (:373-377)
         if (dump_gso_entry(g, L, loop != 0, loop == 0 ? "Input" : hooks.step, loop == 0 ? -1 : loop - 1,
                            loop == 0 ? 0.0 : hooks.seconds(), &rdg[L * d], &rex[L * d], rows[L]) != FPHIP_OK)
-          return gfail_msg(g->ctx, "BKZ_DUMP_GSO: cannot write the dump file");
+          return fail_msg(g->ctx, "BKZ_DUMP_GSO: cannot write the dump file");
       }
       ran[L] = 0;
       if (!active[L])
@@ -2356,6 +2150,93 @@ extern "C" int fphip_gso_bkz_inloop_stats(const fphip_gso *g, unsigned long long
   return FPHIP_OK;
 }
 
+// What the kernel can run of the caller's strategies up to block size bsz: FPHIP_OK, FPHIP_UNSUPPORTED (the caller
+// keeps these on fplll's CPU path) or FPHIP_ERROR with its text
+static int check_strategies(fphip_ctx *ctx, const fphip_strategies *S, fphip_rand_fn rnd, int bsz)
+{
+  if (!rnd)
+  {
+    snprintf(fphip_ctx_errbuf(ctx), 512, "fphip_gso_bkz_strategies: strategies need the caller's generator");
+    return FPHIP_ERROR;
+  }
+  if (S->max_block_size < bsz || !S->pre_off || !S->prune_off || !S->coeff_off)
+  {
+    snprintf(fphip_ctx_errbuf(ctx), 512, "fphip_gso_bkz_strategies: strategies do not cover block size %d", bsz);
+    return FPHIP_ERROR;
+  }
+  // every block size needs a pruning set whose coefficient vector is empty or of that size;
+  // preprocessing block sizes must be proper (2 <= p < b) and nest at most MAX_DEPTH - 1 deep
+  std::vector<int> depth(bsz + 1, 0);
+  for (int b = 0; b <= bsz; ++b)
+  {
+    if (S->prune_off[b + 1] <= S->prune_off[b])
+      return FPHIP_UNSUPPORTED;
+    for (int p = S->prune_off[b]; p < S->prune_off[b + 1]; ++p)
+    {
+      const int len = S->coeff_off[p + 1] - S->coeff_off[p];
+      if (len != 0 && len != b)
+        return FPHIP_UNSUPPORTED;
+    }
+    for (int p = S->pre_off[b]; p < S->pre_off[b + 1]; ++p)
+    {
+      const int pb = S->pre[p];
+      if (pb < 2 || pb >= b)
+        return FPHIP_UNSUPPORTED;
+      // a tour of block size pb reaches every block size <= pb through hkz
+      int dmax = 0;
+      for (int c = 2; c <= pb; ++c)
+        dmax = std::max(dmax, depth[c]);
+      depth[b] = std::max(depth[b], dmax + 1);
+    }
+  }
+  int dtop = 0;
+  for (int b = 2; b <= bsz; ++b)
+    dtop = std::max(dtop, depth[b]);
+  if (dtop + 1 > FPHIP_BKZS_MAX_DEPTH)
+    return FPHIP_UNSUPPORTED;
+  return FPHIP_OK;
+}
+
+// One launch of the strategy kernel the call needs — with u or without, the self-dual / slide variant (dual) or the
+// primal one — at the geometry fphip_gso_bkz_strategies worked out; the kernel is first allowed its dynamic LDS where
+// that exceeds the default limit.  The caller records the events around it and reads hipGetLastError().
+struct BkzsGeometry
+{
+  int nq, wpb, grid, stack_doubles, mu_lds_flag;
+  size_t lds;
+};
+static hipError_t bkzs_launch(fphip_gso *g, const BkzsGeometry &geo, hipStream_t s, bool sd, bool sld,
+                              const BkzStrat &DS, BkzMail *mail, int *d_abort, int block_size, int kflags,
+                              double delta, double eta, double logd, int kloops, int run_mode)
+{
+  const int nq = geo.nq, wpb = geo.wpb, grid = geo.grid, stack_doubles = geo.stack_doubles, mu_lds_flag = geo.mu_lds_flag;
+  const size_t lds = geo.lds;
+  const bool big = lds > 64 * 1024;
+  unsigned long long *us = g->bkz_stats_d;
+  hipError_t e = hipSuccess;
+  if (g->bkz_u && (sd || sld))
+    dispatch_nq(nq, [&](auto NQ) {
+      if (!big || (e = allow_lds(sdv::bkzd_kernel_u<NQ>, lds)) == hipSuccess)
+        hipLaunchKernelGGL(sdv::bkzd_kernel_u<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us);
+    });
+  else if (g->bkz_u)
+    dispatch_nq(nq, [&](auto NQ) {
+      if (!big || (e = allow_lds(bkzs_kernel_u<NQ>, lds)) == hipSuccess)
+        hipLaunchKernelGGL(bkzs_kernel_u<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us);
+    });
+  else if (sd || sld)
+    dispatch_nq(nq, [&](auto NQ) {
+      if (!big || (e = allow_lds(sdv::bkzd_kernel<NQ>, lds)) == hipSuccess)
+        hipLaunchKernelGGL(sdv::bkzd_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode);
+    });
+  else
+    dispatch_nq(nq, [&](auto NQ) {
+      if (!big || (e = allow_lds(bkzs_kernel<NQ>, lds)) == hipSuccess)
+        hipLaunchKernelGGL(bkzs_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles);
+    });
+  return e;
+}
+
 extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double delta, double eta,
                                         int flags, int max_loops, double gh_factor,
                                         const fphip_strategies *S, fphip_rand_fn rnd, void *rnd_user,
@@ -2404,48 +2285,8 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
     flags |= 0x20;  // "SD Variant of BKZ requires explicit termination condition", bkz.cpp:548-554
   const int bsz = block_size < g->P.d ? block_size : g->P.d;
   if (S)
-  {
-    if (!rnd)
-    {
-      snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_gso_bkz_strategies: strategies need the caller's generator");
-      return FPHIP_ERROR;
-    }
-    if (S->max_block_size < bsz || !S->pre_off || !S->prune_off || !S->coeff_off)
-    {
-      snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_gso_bkz_strategies: strategies do not cover block size %d", bsz);
-      return FPHIP_ERROR;
-    }
-    // every block size needs a pruning set whose coefficient vector is empty or of that size;
-    // preprocessing block sizes must be proper (2 <= p < b) and nest at most MAX_DEPTH - 1 deep
-    std::vector<int> depth(bsz + 1, 0);
-    for (int b = 0; b <= bsz; ++b)
-    {
-      if (S->prune_off[b + 1] <= S->prune_off[b])
-        return FPHIP_UNSUPPORTED;
-      for (int p = S->prune_off[b]; p < S->prune_off[b + 1]; ++p)
-      {
-        const int len = S->coeff_off[p + 1] - S->coeff_off[p];
-        if (len != 0 && len != b)
-          return FPHIP_UNSUPPORTED;
-      }
-      for (int p = S->pre_off[b]; p < S->pre_off[b + 1]; ++p)
-      {
-        const int pb = S->pre[p];
-        if (pb < 2 || pb >= b)
-          return FPHIP_UNSUPPORTED;
-        // a tour of block size pb reaches every block size <= pb through hkz
-        int dmax = 0;
-        for (int c = 2; c <= pb; ++c)
-          dmax = std::max(dmax, depth[c]);
-        depth[b] = std::max(depth[b], dmax + 1);
-      }
-    }
-    int dtop = 0;
-    for (int b = 2; b <= bsz; ++b)
-      dtop = std::max(dtop, depth[b]);
-    if (dtop + 1 > FPHIP_BKZS_MAX_DEPTH)
-      return FPHIP_UNSUPPORTED;
-  }
+    if (int rcs = check_strategies(g->ctx, S, rnd, bsz))
+      return rcs;
   int rc = ensure_lll_buffers(g);
   if (rc != FPHIP_OK)
     return rc;
@@ -2489,7 +2330,7 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
     if (e_ != hipSuccess)                  \
     {                                      \
       cleanup();                           \
-      return gfail(g->ctx, #call, e_);     \
+      return fail(g->ctx, #call, e_);     \
     }                                      \
   } while (0)
   if (S)
@@ -2576,44 +2417,7 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
     grid = cap;
   hipStream_t s     = fphip_ctx_stream(g->ctx);
   const double logd = std::log(delta);
-  if (lds > 64 * 1024 && g->bkz_u)
-  {
-    switch (nq)
-    {
-    case 1: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 2: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 3: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    default: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel_u<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    }
-    if (sd || sld)
-      switch (nq)
-      {
-      case 1: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      case 2: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      case 3: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      default: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel_u<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      }
-  }
-  if (lds > 64 * 1024)
-  {
-    switch (nq)
-    {
-    case 1: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 2: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 3: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    default: BCHK(hipFuncSetAttribute((const void *)bkzs_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    }
-  }
-  if ((sd || sld) && lds > 64 * 1024)
-  {
-    switch (nq)
-    {
-    case 1: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 2: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    case 3: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    default: BCHK(hipFuncSetAttribute((const void *)sdv::bkzd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    }
-  }
+  const BkzsGeometry geo{nq, wpb, grid, stack_doubles, mu_lds_flag, lds};
   BkzsHost H{S, gh_factor, rnd, rnd_user, 0.0};
   // in-loop pruning: a pool of worker threads (one prune() is tens of milliseconds; the lattices of a batch
   // ask at about the same time), each with a volume engine of its own (stream, staging, device buffers)
@@ -2728,46 +2532,7 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
       return rc1;
     GCHK(hipMemsetAsync(d_abort, 0, sizeof(int), s));  // one launch's timeout must not poison the next
     GCHK(hipEventRecord(g->ev[0], s));
-    if (g->bkz_u && (sd || sld))
-    {
-      unsigned long long *us = g->bkz_stats_d;
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL(sdv::bkzd_kernel_u<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
-      case 2: hipLaunchKernelGGL(sdv::bkzd_kernel_u<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
-      case 3: hipLaunchKernelGGL(sdv::bkzd_kernel_u<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
-      default: hipLaunchKernelGGL(sdv::bkzd_kernel_u<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode, us); break;
-      }
-    }
-    else if (g->bkz_u)
-    {
-      unsigned long long *us = g->bkz_stats_d;
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL(bkzs_kernel_u<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
-      case 2: hipLaunchKernelGGL(bkzs_kernel_u<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
-      case 3: hipLaunchKernelGGL(bkzs_kernel_u<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
-      default: hipLaunchKernelGGL(bkzs_kernel_u<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, us); break;
-      }
-    }
-    else if (sd || sld)
-    {
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL(sdv::bkzd_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode); break;
-      case 2: hipLaunchKernelGGL(sdv::bkzd_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode); break;
-      case 3: hipLaunchKernelGGL(sdv::bkzd_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode); break;
-      default: hipLaunchKernelGGL(sdv::bkzd_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | (sd ? 0x100 : 0) | mu_lds_flag, delta, eta, logd, kloops, stack_doubles, run_mode); break;
-      }
-    }
-    else
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL(bkzs_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles); break;
-    case 2: hipLaunchKernelGGL(bkzs_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles); break;
-    case 3: hipLaunchKernelGGL(bkzs_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles); break;
-    default: hipLaunchKernelGGL(bkzs_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, g->P, DS, mail, d_abort, block_size, kflags | mu_lds_flag, delta, eta, logd, kloops, stack_doubles); break;
-    }
+    GCHK(bkzs_launch(g, geo, s, sd, sld, DS, mail, d_abort, block_size, kflags, delta, eta, logd, kloops, run_mode));
     GCHK(hipGetLastError());
     GCHK(hipEventRecord(g->ev[1], s));
     // Serve the mailboxes while the kernel runs, from a thread of its own that makes NO HIP call:
@@ -2888,7 +2653,7 @@ extern "C" int fphip_gso_bkz_strategies(fphip_gso *g, int block_size, double del
         t.join();
     }
     if (q != hipSuccess)
-      return gfail(g->ctx, "bkzs_kernel", q);
+      return fail(g->ctx, "bkzs_kernel", q);
     GCHK(hipEventElapsedTime(ms, g->ev[0], g->ev[1]));
     GCHK(hipMemcpy(st_out, g->P.status, sizeof(int) * B, hipMemcpyDeviceToHost));
     GCHK(hipMemcpy(info_out, g->P.lll_info, sizeof(int) * 4 * B, hipMemcpyDeviceToHost));
@@ -3178,11 +2943,11 @@ extern "C" int fphip_gso_babai(fphip_gso *g, int lattice, int T, const double *v
     return rc;
   const int d = g->P.d;
   if (start < 0 || start >= d)
-    return gfail_msg(g->ctx, "fphip_gso_babai: start outside the basis");
+    return fail_msg(g->ctx, "fphip_gso_babai: start outside the basis");
   if (dimension == -1)
     dimension = d - start;
   if (dimension < 1 || start + dimension > d)
-    return gfail_msg(g->ctx, "fphip_gso_babai: rows [start, start + dimension) outside the basis");
+    return fail_msg(g->ctx, "fphip_gso_babai: rows [start, start + dimension) outside the basis");
   const size_t ldt = ((size_t)T + 63) / 64 * 64, dm = (size_t)dimension;
   hipStream_t s = fphip_ctx_stream(g->ctx);
   CvpBufs B(s);
@@ -3266,7 +3031,7 @@ extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, 
   if (int rc = fphip_gso_update(g, gst.data()))
     return rc;
   if (gst[lattice] != 1)
-    return gfail_msg(g->ctx, "fphip_closest_vector: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
+    return fail_msg(g->ctx, "fphip_closest_vector: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
   const size_t dd = (size_t)d;
   std::vector<int64_t> coef((size_t)T * dd);
   std::vector<double> tc((size_t)T * dd), desc((size_t)T), mu(dd * dd), rd(dd), mut(dd * dd, 0.0), xr(dd);
@@ -3410,7 +3175,7 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
   if (int rc = cvp_lattice_guard(g, lattice, 1, "fphip_list_vectors"))
     return rc;
   if (bound_sq < 0)
-    return gfail_msg(g->ctx, "fphip_list_vectors: a negative bound");
+    return fail_msg(g->ctx, "fphip_list_vectors: a negative bound");
   const int d = g->P.d;
   const size_t dd = (size_t)d, n = (size_t)g->P.n;
   if (d > 64)
@@ -3422,7 +3187,7 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
   if (int rc = fphip_gso_update(g, gst.data()))
     return rc;
   if (gst[lattice] != 1)
-    return gfail_msg(g->ctx, "fphip_list_vectors: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
+    return fail_msg(g->ctx, "fphip_list_vectors: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
   std::vector<double> mu(dd * dd), rd(dd), bfd(dd * n), mut(dd * dd, 0.0), tc(dd, 0.0);
   {
     hipStream_t s = fphip_ctx_stream(g->ctx);
@@ -3471,7 +3236,7 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
     if (found <= icap)
       break;
     if (attempt > 0)
-      return gfail_msg(g->ctx, "fphip_list_vectors: the list changed its length between two enumerations");
+      return fail_msg(g->ctx, "fphip_list_vectors: the list changed its length between two enumerations");
     icap = found;
   }
   if (found == 0)
@@ -3481,7 +3246,7 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
   for (size_t i = 0; i < (size_t)found * dd; ++i)
   {
     if (!(std::fabs(lx[i]) < 9223372036854775808.0))
-      return gfail_msg(g->ctx, "fphip_list_vectors: a coefficient beyond the int64 range");
+      return fail_msg(g->ctx, "fphip_list_vectors: a coefficient beyond the int64 range");
     rc_coef[i] = (int64_t)lx[i];
   }
   if (int rc = list_vectors_run(g, lattice, found, rc_coef.data(), target, rvec.data(), rnorm.data(), rst.data()))
@@ -3519,10 +3284,6 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
 extern "C" double fphip_gso_last_kernel_ms(const fphip_gso *g) { return g ? g->last_ms : 0.0; }
 
 // FETCH_SIZE calibration (not part of the product ABI; used by tests/perf/calib_fetch.py only)
-namespace fphip
-{
-__global__ void gso_calib_kernel(const char *buf, size_t stride, int row_bytes, long long rows);
-}
 extern "C" int fphip_debug_stream(fphip_ctx *ctx, long long rows, int row_bytes, long long stride,
                                   double *ms_out)
 {
@@ -3555,14 +3316,6 @@ extern "C" int fphip_debug_stream(fphip_ctx *ctx, long long rows, int row_bytes,
 // Batched Householder R-factor: MatHouseholder<Z_NR<long>, FP_NR<double>> refresh_R_bf() +
 // update_R() (fplll/householder.h:532-536, 610-614)
 // ---------------------------------------------------------------------------------------------
-namespace fphip
-{
-template <int NQ> __global__ void hh_update_kernel(HhBatch P);
-template <int NT> __global__ void hh_rows_kernel(HhBatch P);
-__global__ void hh_size_reduce_kernel(HhBatch P, int k, int end, int start, int *reduced);
-__global__ void hh_size_reduce_u_kernel(HhBatch P, int k, int end, int start, int *reduced, long long *Uall, int ldu);
-}
-
 struct fphip_hh
 {
   fphip_ctx *ctx;
@@ -3582,13 +3335,7 @@ struct fphip_hh
   int ldu      = 0;
 };
 
-#define HCHK(call)                     \
-  do                                   \
-  {                                    \
-    hipError_t e_ = (call);            \
-    if (e_ != hipSuccess)              \
-      return gfail(h->ctx, #call, e_); \
-  } while (0)
+#define HCHK(call) CHK(h->ctx, call)
 
 static int hh_allocate(fphip_hh *h);
 extern "C" void fphip_hh_destroy(fphip_hh *h);
@@ -3810,13 +3557,7 @@ extern "C" int fphip_hh_update_R(fphip_hh *h, int *status)
     }
   }
   else
-  switch (nq)
-  {
-  case 1: hipLaunchKernelGGL(hh_update_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, h->P); break;
-  case 2: hipLaunchKernelGGL(hh_update_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, h->P); break;
-  case 3: hipLaunchKernelGGL(hh_update_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, h->P); break;
-  default: hipLaunchKernelGGL(hh_update_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, h->P); break;
-  }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(hh_update_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, h->P); });
   HCHK(hipGetLastError());
   HCHK(hipEventRecord(h->ev[1], s));
   HCHK(hipStreamSynchronize(s));
@@ -3891,13 +3632,7 @@ extern "C" int fphip_hh_update_R_blocked(fphip_hh *h, int *status)
     grid = fphip_ctx_num_cus(h->ctx) * bpc;
   hipStream_t s = fphip_ctx_stream(h->ctx);
   HCHK(hipEventRecord(h->ev[0], s));
-  switch (nq)
-  {
-  case 1: hipLaunchKernelGGL(hh_blocked_kernel<1>, dim3(grid), dim3(64), lds, s, h->P, h->Tbuf); break;
-  case 2: hipLaunchKernelGGL(hh_blocked_kernel<2>, dim3(grid), dim3(64), lds, s, h->P, h->Tbuf); break;
-  case 3: hipLaunchKernelGGL(hh_blocked_kernel<3>, dim3(grid), dim3(64), lds, s, h->P, h->Tbuf); break;
-  default: hipLaunchKernelGGL(hh_blocked_kernel<4>, dim3(grid), dim3(64), lds, s, h->P, h->Tbuf); break;
-  }
+  dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(hh_blocked_kernel<NQ>, dim3(grid), dim3(64), lds, s, h->P, h->Tbuf); });
   HCHK(hipGetLastError());
   HCHK(hipEventRecord(h->ev[1], s));
   HCHK(hipStreamSynchronize(s));
@@ -3950,21 +3685,9 @@ extern "C" int fphip_hh_hlll(fphip_hh *h, double delta, double eta, double theta
   hipStream_t s = fphip_ctx_stream(h->ctx);
   HCHK(hipEventRecord(h->ev[0], s));
   if (h->u)  // the transformation matrix is tracked: the u-carrying kernel (hlll_kernel_u.hip), same launch shape
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL(hlll_u_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
-    case 2: hipLaunchKernelGGL(hlll_u_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
-    case 3: hipLaunchKernelGGL(hlll_u_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
-    default: hipLaunchKernelGGL(hlll_u_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); break;
-    }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(hlll_u_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap, h->u, h->ldu); });
   else
-  switch (nq)
-  {
-  case 1: hipLaunchKernelGGL(hlll_kernel<1>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap); break;
-  case 2: hipLaunchKernelGGL(hlll_kernel<2>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap); break;
-  case 3: hipLaunchKernelGGL(hlll_kernel<3>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap); break;
-  default: hipLaunchKernelGGL(hlll_kernel<4>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap); break;
-  }
+    dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(hlll_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, h->P, delta, theta, cap); });
   HCHK(hipGetLastError());
   HCHK(hipEventRecord(h->ev[1], s));
   HCHK(hipStreamSynchronize(s));
@@ -4066,56 +3789,15 @@ static int hh_hlll_ex(fphip_hh *h, double delta, double theta, int precision, co
   hipStream_t s = fphip_ctx_stream(h->ctx);
   HCHK(hipEventRecord(h->ev[0], s));
   if (h->u)  // the transformation matrix is tracked: the u-carrying kernels (hlll_x_u.hip)
-  {
-    if (precision == 212)
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL((hlll_x_u_kernel<1, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      case 2: hipLaunchKernelGGL((hlll_x_u_kernel<2, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      case 3: hipLaunchKernelGGL((hlll_x_u_kernel<3, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      default: hipLaunchKernelGGL((hlll_x_u_kernel<4, QD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      }
-    else if (precision == 106)
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL((hlll_x_u_kernel<1, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      case 2: hipLaunchKernelGGL((hlll_x_u_kernel<2, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      case 3: hipLaunchKernelGGL((hlll_x_u_kernel<3, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      default: hipLaunchKernelGGL((hlll_x_u_kernel<4, DD>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      }
-    else
-      switch (nq)
-      {
-      case 1: hipLaunchKernelGGL((hlll_x_u_kernel<1, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      case 2: hipLaunchKernelGGL((hlll_x_u_kernel<2, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      case 3: hipLaunchKernelGGL((hlll_x_u_kernel<3, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      default: hipLaunchKernelGGL((hlll_x_u_kernel<4, double>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); break;
-      }
-  }
-  else if (precision == 212)
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL((hlll_x_kernel<1, QD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    case 2: hipLaunchKernelGGL((hlll_x_kernel<2, QD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    case 3: hipLaunchKernelGGL((hlll_x_kernel<3, QD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    default: hipLaunchKernelGGL((hlll_x_kernel<4, QD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    }
-  else if (precision == 106)
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL((hlll_x_kernel<1, DD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    case 2: hipLaunchKernelGGL((hlll_x_kernel<2, DD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    case 3: hipLaunchKernelGGL((hlll_x_kernel<3, DD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    default: hipLaunchKernelGGL((hlll_x_kernel<4, DD>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    }
+    dispatch_precision(precision, [&](auto ft) {
+      using FT = typename decltype(ft)::type;
+      dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL((hlll_x_u_kernel<NQ, FT>), dim3(grid), dim3(64), 0, s, h->P, X, h->u, h->ldu); });
+    });
   else
-    switch (nq)
-    {
-    case 1: hipLaunchKernelGGL((hlll_x_kernel<1, double>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    case 2: hipLaunchKernelGGL((hlll_x_kernel<2, double>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    case 3: hipLaunchKernelGGL((hlll_x_kernel<3, double>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    default: hipLaunchKernelGGL((hlll_x_kernel<4, double>), dim3(grid), dim3(64), 0, s, h->P, X); break;
-    }
+    dispatch_precision(precision, [&](auto ft) {
+      using FT = typename decltype(ft)::type;
+      dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL((hlll_x_kernel<NQ, FT>), dim3(grid), dim3(64), 0, s, h->P, X); });
+    });
   HCHK(hipGetLastError());
   HCHK(hipEventRecord(h->ev[1], s));
   HCHK(hipStreamSynchronize(s));

@@ -28,6 +28,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no FMA contraction).
 
 #include "gso_wave.h"
+#include "kernels.h"
 
 namespace fphip
 {

@@ -24,6 +24,7 @@
 #include <limits.h>
 
 #include "gso_device.h"
+#include "kernels.h"
 
 namespace fphip
 {

@@ -32,6 +32,7 @@
 // line of it is compiled out: hlll_kernel<NQ> is the output of its own translation unit, as before.
 
 #include "gso_wave.h"
+#include "kernels.h"
 
 #ifdef FPHIP_HLLL_U
 #define FPHIP_HLLL_KERNEL hlll_u_kernel

@@ -27,6 +27,7 @@
 // it is compiled out, and the unit-test kernels below belong to this translation unit alone.
 #include "ftx.h"
 #include "gso_device.h"
+#include "kernels.h"
 
 #ifdef FPHIP_HLLL_X_U
 #define FPHIP_HLLL_X_KERNEL hlll_x_u_kernel
@@ -70,22 +71,7 @@ template <> struct Plane<QD>
   }
 };
 
-struct HlllX
-{
-  // R, V: [batch][d][ldn] in up to four planes each (P.R / P.V, Rlo / Vlo, and for quad-double Rx / Vx: two more
-  // planes back to back); bf has no low part
-  double *Rlo, *Vlo;
-  // per lattice scalars, [batch][d] each: norm_square_b, dR, eR, prev_R, R(i,i) (four component planes each)
-  double *sc;  // [batch][20][d]
-  long long *prevE;
-  double delta, theta;
-  long long iter_cap;
-  const int *only_failed;  // precision ladder: non-null = reduce only lattices whose entry is not 1
-  // blocked application of the reflectors (compact WY, householder.cpp:151-184 sixteen reflectors at a time):
-  // T of every block of 16 reflectors, [batch][ceil(d / 16)][16][16] (hi / lo planes); null = one by one
-  double *Thi, *Tlo;
-  double *Rx, *Vx;  // quad-double: components 2 and 3 of R and V ([2][batch][d][ldn] each)
-};
+// (HlllX, the kernel's second argument: kernels.h)
 
 // status: 1 RED_SUCCESS, -2 multiplier beyond 63 bits, -4 RED_HLLL_SR_FAILURE,
 //         -5 RED_HLLL_NORM_FAILURE, -6 iteration cap.  info[2] per lattice: swaps, loop iterations

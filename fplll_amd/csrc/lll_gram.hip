@@ -37,6 +37,7 @@
 
 #include "gram_device.h"
 #include "lll_wave.h"
+#include "kernels.h"
 
 namespace fphip
 {

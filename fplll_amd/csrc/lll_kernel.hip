@@ -31,6 +31,7 @@
 // identity-layout GSO with the sweep kernel, which yields the same values.
 
 #include "lll_wave.h"
+#include "kernels.h"
 
 namespace fphip
 {

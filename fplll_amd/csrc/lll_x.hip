@@ -32,6 +32,7 @@
 // before.
 #include "ftx.h"
 #include "gso_device.h"
+#include "kernels.h"
 
 #ifdef FPHIP_LLL_X_U
 #define FPHIP_LLL_X_KERNEL lll_x_u_kernel
@@ -44,22 +45,7 @@
 namespace fphip
 {
 
-struct LllX
-{
-  int batch, d, n, ldn, ldd, row_expo;
-  long long *b, *b2;      // [batch][d][ldn]: rows by slot; b2: output, rows in position order
-  double *bf;             // [batch][d][ldn]
-  double *mu_hi, *mu_lo;  // [batch][d][ldd]: row = slot, column = position
-  double *r_hi, *r_lo;
-  double *gf_hi, *gf_lo;  // [batch][d][ldd]: Gram cache, entry (max slot, min slot); hi NaN = unknown
-  double *mu_x, *r_x, *gf_x;  // quad-double: components 2 and 3 of the three arrays (two planes back to back each)
-  long long *rexp;        // [batch][d] by slot
-  int *status, *info;     // info[4]: final_kappa, n_swaps, zeros, iterations
-  const int *only_failed; // precision ladder: non-null = only the lattices whose entry is not 1
-  int kmin, kstart, kend;
-  double delta, eta;
-  int *slot_out;          // null, or [batch][d]: the slot of every position at the end (the key of the rows of mu / r)
-};
+// (LllX, the kernel's argument: kernels.h)
 
 template <class FT> struct PlaneX;
 template <> struct PlaneX<double>
