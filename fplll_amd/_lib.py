@@ -103,6 +103,23 @@ def load():
     return lib
 
 
+# fphip_shortest_vector: method, flags (fplll's SVPMethod / SVPFlags) and route
+SVPM_FAST = 0
+SVPM_PROVED = 2
+SVP_OVERRIDE_BND = 2
+SVP_DUAL = 4
+SVP_ROUTES = {"auto": 0, "wave": 1, "enum": 2}
+
+
+def bind_shortest_vector(lib):
+    """Prototype of fphip_shortest_vector (g, ectx, first_lattice, count, method, flags, pruning, route, sol_coord,
+    vec, norm, nodes, status)."""
+    vp = ctypes.c_void_p
+    lib.fphip_shortest_vector.restype = ctypes.c_int
+    lib.fphip_shortest_vector.argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp, ctypes.c_int] + [vp] * 5
+    return lib.fphip_shortest_vector
+
+
 class HipError(RuntimeError):
     pass
 

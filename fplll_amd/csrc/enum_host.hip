@@ -170,7 +170,7 @@ static int fail(fphip_ctx *ctx, const char *fmt, ...)
       return fail(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" int fphip_abi_version(void) { return 5; }
+extern "C" int fphip_abi_version(void) { return 6; }
 
 extern "C" int fphip_device_count(void)
 {
@@ -512,6 +512,18 @@ static void estimate_levels(int d, const double *rdiag, const double *pruning, d
     double logV = 0.5 * n * std::log(M_PI) - std::lgamma(0.5 * n + 1.0);
     logN[k]     = std::log(0.5) + logV + 0.5 * n * std::log(R2 > 0 ? R2 : 1e-300) - sumlog;
   }
+}
+
+// the estimate's total over the levels: what min_nodes_decline is compared with, and what the shortest-vector
+// solver's AUTO route (gso_host.hip) compares with its threshold
+double fphip_enum_gh_nodes(int d, const double *rdiag, const double *pruning, double maxdist)
+{
+  double logN[FPHIP_ENUM_MAX_DIM + 1];
+  estimate_levels(d, rdiag, pruning, maxdist, logN);
+  double tot = 0;
+  for (int k = 0; k < d; ++k)
+    tot += std::exp(std::min(logN[k], 700.0));
+  return tot;
 }
 
 // level at which to cut next, or -1 to walk to the leaves

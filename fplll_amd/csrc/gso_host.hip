@@ -3109,6 +3109,360 @@ extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, 
   return FPHIP_OK;
 }
 
+// ---- shortest vectors (svp_wave.hip; the ENUM route: fphip_enum_run) -----------------------------------------------
+namespace
+{
+// The default of FPHIP_SVP_WAVE_MAX_NODES: the Gaussian-heuristic node estimate (radius min(r_00, GH^2)) up to which
+// the AUTO route gives a lattice to the wave-per-lattice kernel.  Measured (profiles/svp_solver.md, LLL-reduced q-ary
+// lattices, batch 1024): at d = 32 (estimate 5.8e4) WAVE takes 0.179 ms per lattice against ENUM's 0.625 ms, at d = 40
+// (estimate 5.0e6) 31.9 ms against 1.43 ms; the two times are equal at an estimate of 2.08e5 (log-log interpolation).
+// 0 would mean no limit.
+constexpr double SVP_WAVE_MAX_NODES_DEFAULT = 2.0e5;
+
+typedef __int128 i128;
+// the ENUM route's evaluator: the candidate's exact norm in 128-bit integers, strictly smaller wins, the bound
+// follows as (N - 1) (1 + 2^-30)
+struct SvpBest
+{
+  int d, n;              // rows under enumeration (d_eff), columns
+  const long long *b;    // [d][n] host copy of the rows
+  long long nbest;
+  bool overflow;
+  std::vector<long long> x, v;
+  std::vector<i128> w;
+  double bound() const { return (double)(nbest - 1) * (1.0 + 0x1p-30); }
+};
+// false: a product or a sum left the 127-bit range, or the result the int64 range
+bool svp_exact_candidate(SvpBest *B, const double *sol, long long *norm)
+{
+  const int d = B->d, n = B->n;
+  std::fill(B->w.begin(), B->w.end(), (i128)0);
+  for (int i = 0; i < d; ++i)
+  {
+    if (sol[i] == 0.0)
+      continue;
+    if (!(std::fabs(sol[i]) < 9223372036854775808.0))
+      return false;
+    const i128 xi = (i128)(long long)sol[i];
+    for (int j = 0; j < n; ++j)
+    {
+      i128 p, q;
+      if (__builtin_mul_overflow(xi, (i128)B->b[(size_t)i * n + j], &p) || __builtin_add_overflow(B->w[j], p, &q))
+        return false;
+      B->w[j] = q;
+    }
+  }
+  i128 nrm = 0;
+  for (int j = 0; j < n; ++j)
+  {
+    i128 p, q;
+    if (__builtin_mul_overflow(B->w[j], B->w[j], &p) || __builtin_add_overflow(nrm, p, &q))
+      return false;
+    nrm = q;
+  }
+  if (nrm > (i128)std::numeric_limits<long long>::max())
+    return false;
+  *norm = (long long)nrm;
+  return true;
+}
+double svp_best_cb(void *user, double dist, const double *sol)
+{
+  (void)dist;  // (the decision is the integers')
+  SvpBest *B = (SvpBest *)user;
+  long long nv = 0;
+  if (!svp_exact_candidate(B, sol, &nv))
+  {
+    B->overflow = true;
+    return 0.0;  // stop
+  }
+  if (nv > 0 && nv < B->nbest)
+  {
+    B->nbest = nv;
+    for (int i = 0; i < B->d; ++i)
+      B->x[i] = (long long)sol[i];
+    for (int j = 0; j < B->n; ++j)
+      B->v[j] = (long long)B->w[j];
+  }
+  return B->bound();  // (0 once the norm is 1: nothing non-zero is shorter)
+}
+
+// last_useful_index (svpcvp.cpp:32-43) on the true r_ii
+int svp_last_useful_index(int d, const double *rd)
+{
+  int i;
+  for (i = d - 1; i > 0; --i)
+    if (rd[i] <= 2.0 * rd[0])
+      break;
+  return i + 1;
+}
+}  // namespace
+
+// the wave-per-lattice kernel over the range; skip (device, nullable): lattices it leaves alone
+static int svp_wave_run(fphip_gso *g, int first, int count, const double *pruning, const int *take_h, int64_t *sol_coord,
+                        int64_t *vec, int64_t *norm, uint64_t *nodes, int *status)
+{
+  const size_t d = g->P.d, n = g->P.n;
+  const int nq   = (int)((std::max(d, n) + 63) / 64);
+  int wpb        = 4;
+  SvpWave A;
+  memset(&A, 0, sizeof A);
+  A.first = first, A.count = count;
+  A.stack_doubles = (int)(d * (d + 1) / 2 + 2);
+  A.mu_doubles    = (int)std::max<size_t>(d * (d - 1) / 2, 2);
+  const size_t per_wave = (size_t)(A.stack_doubles + A.mu_doubles) * sizeof(double);
+  const size_t lds      = per_wave * wpb;  // d <= 64: at most 131136 bytes
+  int bpc = (int)((160 * 1024) / lds);
+  if (bpc * wpb > 32)
+    bpc = 32 / wpb;
+  int grid = (count + wpb - 1) / wpb;
+  int cap  = fphip_ctx_num_cus(g->ctx) * std::max(bpc, 1);
+  if (const char *e = getenv("FPHIP_SVP_WAVE_GRID"))  // (tests: a small grid makes a small batch go round the grid-stride loop)
+    cap = std::max(1, atoi(e));
+  grid = std::min(grid, cap);
+  hipStream_t s = fphip_ctx_stream(g->ctx);
+  CvpBufs B(s);
+  double *pr_d = nullptr;
+  int *take_d  = nullptr;
+  GCHK(B.get(&A.sol_coord, (size_t)count * d));
+  GCHK(B.get(&A.vec, (size_t)count * n));
+  GCHK(B.get(&A.norm, (size_t)count));
+  GCHK(B.get(&A.nodes, (size_t)count));
+  GCHK(B.get(&A.status, (size_t)count));
+  if (pruning)
+  {
+    GCHK(B.get(&pr_d, d));
+    GCHK(hipMemcpy(pr_d, pruning, d * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (take_h)
+  {
+    GCHK(B.get(&take_d, (size_t)count));
+    GCHK(hipMemcpy(take_d, take_h, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+  }
+  GCHK(hipStreamSynchronize(nullptr));  // (see fphip_gso_set_basis)
+  A.pruning = pr_d;
+  A.take    = take_d;
+  if (lds > 64 * 1024)
+    GCHK(dispatch_nq(nq, [&](auto NQ) { return allow_lds(svp_wave_kernel<NQ>, lds); }));
+  GCHK(hipEventRecord(g->ev[0], s));
+  dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(svp_wave_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, A); });
+  GCHK(hipGetLastError());
+  GCHK(hipEventRecord(g->ev[1], s));
+  GCHK(hipStreamSynchronize(s));
+  GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  std::vector<long long> hs((size_t)count * d), hv((size_t)count * n), hn((size_t)count);
+  std::vector<unsigned long long> hk((size_t)count);
+  std::vector<int> ht((size_t)count);
+  GCHK(hipMemcpy(hs.data(), A.sol_coord, hs.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(hv.data(), A.vec, hv.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(hn.data(), A.norm, hn.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(hk.data(), A.nodes, hk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(ht.data(), A.status, ht.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int w = 0; w < count; ++w)
+  {
+    if (take_h && !take_h[w])
+      continue;
+    memcpy(sol_coord + (size_t)w * d, &hs[(size_t)w * d], d * sizeof(int64_t));
+    memcpy(vec + (size_t)w * n, &hv[(size_t)w * n], n * sizeof(int64_t));
+    norm[w] = hn[w], nodes[w] = hk[w], status[w] = ht[w];
+  }
+  return FPHIP_OK;
+}
+
+// one lattice by the enumerator: true mu and r, row norms / last_useful_index / the initial answer on the host
+static int svp_enum_one(fphip_gso *g, fphip_ctx *ectx, int lattice, const double *pruning, int64_t *sol, int64_t *vec,
+                        int64_t *norm, uint64_t *nodes, int *status)
+{
+  const int d = g->P.d, n = g->P.n;
+  const size_t dd = (size_t)d, nn = (size_t)n;
+  memset(sol, 0, dd * sizeof(int64_t));
+  memset(vec, 0, nn * sizeof(int64_t));
+  *norm = 0, *nodes = 0, *status = 1;
+  std::vector<double> mu(dd * dd), rd(dd);
+  std::vector<long long> bh(dd * nn);
+  {
+    hipStream_t s = fphip_ctx_stream(g->ctx);
+    CvpBufs B(s);
+    double *bfd_d = nullptr, *mu_d = nullptr, *rd_d = nullptr;
+    if (int rc = cvp_unscale(g, lattice, B, &bfd_d, &mu_d, &rd_d))
+      return rc;
+    GCHK(hipStreamSynchronize(s));
+    GCHK(hipMemcpy(mu.data(), mu_d, dd * dd * sizeof(double), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(rd.data(), rd_d, dd * sizeof(double), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy2D(bh.data(), nn * 8, g->P.b + (size_t)lattice * dd * g->P.ldn, (size_t)g->P.ldn * 8, nn * 8, dd,
+                     hipMemcpyDeviceToHost));
+  }
+  std::vector<long long> rn(dd);
+  for (size_t i = 0; i < dd; ++i)
+  {
+    i128 acc = 0;
+    for (size_t j = 0; j < nn && acc <= (i128)std::numeric_limits<long long>::max(); ++j)
+      acc += (i128)bh[i * nn + j] * (i128)bh[i * nn + j];  // (a square is at most 2^126: one more fits the 127 bits)
+    if (acc > (i128)std::numeric_limits<long long>::max())
+    {
+      *status = -2;
+      return FPHIP_OK;
+    }
+    rn[i] = (long long)acc;
+  }
+  const int d_eff = svp_last_useful_index(d, rd.data());
+  int i0 = 0;
+  for (int i = 1; i < d_eff; ++i)
+    if (rn[i] < rn[i0])
+      i0 = i;
+  SvpBest best{d_eff, n, bh.data(), rn[i0], false, std::vector<long long>(dd, 0),
+               std::vector<long long>(bh.begin() + (size_t)i0 * nn, bh.begin() + (size_t)(i0 + 1) * nn),
+               std::vector<i128>(nn)};
+  best.x[i0] = 1;
+  if (d_eff >= 2 && best.bound() > 0.0)
+  {
+    const size_t de = (size_t)d_eff;
+    std::vector<double> mut(de * de, 0.0);
+    for (size_t i = 0; i < de; ++i)
+      for (size_t j = i + 1; j < de; ++j)
+        mut[i * de + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
+    fphip_enum_opts o;
+    memset(&o, 0, sizeof o);
+    o.shard_count       = 1;
+    o.exchange_chunks   = 1;
+    o.min_nodes_decline = 0;  // a shortest-vector call can be declined for being small: never here
+    std::vector<uint64_t> nd(FPHIP_ENUM_MAX_DIM + 1, 0);
+    const int rc = fphip_enum_run(ectx, d_eff, best.bound(), mut.data(), rd.data(), pruning, &o, svp_best_cb, nullptr,
+                                  &best, nd.data(), nullptr);
+    if (rc != FPHIP_OK)
+    {
+      if (ectx != g->ctx)
+        snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_shortest_vector: enumeration of lattice %d: %s", lattice,
+                 fphip_last_error(ectx));
+      return rc;
+    }
+    for (int k = 0; k <= d_eff; ++k)
+      *nodes += nd[k];
+  }
+  if (best.overflow)
+  {
+    *status = -2;
+    *nodes  = 0;
+    return FPHIP_OK;
+  }
+  memcpy(sol, best.x.data(), dd * sizeof(int64_t));
+  memcpy(vec, best.v.data(), nn * sizeof(int64_t));
+  *norm = best.nbest;
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_shortest_vector(fphip_gso *g, fphip_ctx *ectx, int first_lattice, int count, int method, int flags,
+                                     const double *pruning, int route, int64_t *sol_coord, int64_t *vec, int64_t *norm,
+                                     uint64_t *nodes, int *status)
+{
+  FPHIP_RANGE("fphip_shortest_vector");
+  if (!g)
+    return FPHIP_ERROR;
+  if (!sol_coord || !vec || !norm || !nodes || !status)
+    return fail_msg(g->ctx, "fphip_shortest_vector: sol_coord, vec, norm, nodes and status are all required");
+  if (!ectx)
+    ectx = g->ctx;
+  if (first_lattice < 0 || count <= 0 || first_lattice > g->P.batch - count)
+    return fail_msg(g->ctx, "fphip_shortest_vector: lattices [first_lattice, first_lattice + count) outside the batch");
+  if (int rcg = session_guard(g, "fphip_shortest_vector"))
+    return rcg;
+  char *err = fphip_ctx_errbuf(g->ctx);
+  if (method != FPHIP_SVPM_FAST)
+  {
+    snprintf(err, 512, "fphip_shortest_vector: method %d (SVPM_PROVED and its exact evaluator, or an unknown one) is not "
+             "offered: SVPM_FAST only", method);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (flags != 0)
+  {
+    snprintf(err, 512, "fphip_shortest_vector: flags 0x%x (SVP_DUAL, SVP_OVERRIDE_BND, or unknown ones) are not offered: "
+             "0 only", flags);
+    return FPHIP_UNSUPPORTED;
+  }
+  const int d = g->P.d;
+  if (route != FPHIP_SVP_ROUTE_AUTO && route != FPHIP_SVP_ROUTE_WAVE && route != FPHIP_SVP_ROUTE_ENUM)
+    return fail_msg(g->ctx, "fphip_shortest_vector: unknown route");
+  if (route == FPHIP_SVP_ROUTE_WAVE && d > 64)
+  {
+    snprintf(err, 512, "fphip_shortest_vector: the WAVE route takes at most 64 rows (d = %d): use the ENUM route", d);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (d > FPHIP_ENUM_MAX_DIM)
+  {
+    snprintf(err, 512, "fphip_shortest_vector: more than %d rows", FPHIP_ENUM_MAX_DIM);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (pruning)
+    for (int i = 0; i < d; ++i)
+      if (!(pruning[i] > 0.0) || !std::isfinite(pruning[i]))
+        return fail_msg(g->ctx, "fphip_shortest_vector: a pruning coefficient that is not a positive finite number");
+  std::vector<int> gst(g->P.batch, 0);
+  if (int rc = fphip_gso_update(g, gst.data()))
+    return rc;
+  g->last_ms = 0.0f;
+  // the route of every lattice of the range: 1 = WAVE
+  std::vector<int> take((size_t)count, route == FPHIP_SVP_ROUTE_ENUM || d > 64 ? 0 : 1);
+  if (route == FPHIP_SVP_ROUTE_AUTO && d <= 64)
+  {
+    const char *e    = getenv("FPHIP_SVP_WAVE_MAX_NODES");
+    const double lim = e ? atof(e) : SVP_WAVE_MAX_NODES_DEFAULT;
+    if (lim > 0.0)
+    {
+      const size_t dd = (size_t)d;
+      std::vector<double> rs((size_t)count * dd);
+      std::vector<long long> es((size_t)count * dd);
+      GCHK(hipMemcpy(rs.data(), g->P.rdg + (size_t)first_lattice * dd, rs.size() * sizeof(double), hipMemcpyDeviceToHost));
+      GCHK(hipMemcpy(es.data(), g->P.rexp + (size_t)first_lattice * dd, es.size() * sizeof(long long), hipMemcpyDeviceToHost));
+      std::vector<double> rd(dd);
+      for (int w = 0; w < count; ++w)
+      {
+        if (gst[first_lattice + w] != 1)
+          continue;  // (the kernel reports it)
+        for (size_t i = 0; i < dd; ++i)
+          rd[i] = std::ldexp(rs[(size_t)w * dd + i], g->P.row_expo ? (int)(2 * es[(size_t)w * dd + i]) : 0);
+        const int d_eff = svp_last_useful_index(d, rd.data());
+        bool pos = true;
+        for (int i = 0; i < d_eff; ++i)
+          pos = pos && rd[i] > 0.0 && std::isfinite(rd[i]);
+        if (!pos)
+          continue;
+        // the radius of the estimate: r_00, or the squared Gaussian-heuristic length of the lattice where that is
+        // smaller — the walk's radius falls to about that length early, and r_00 can be several times it
+        double logdet = 0.0;
+        for (int i = 0; i < d_eff; ++i)
+          logdet += std::log(rd[i]);
+        const double gh2 = std::exp((2.0 / d_eff) * (std::lgamma(0.5 * d_eff + 1.0) - 0.5 * d_eff * std::log(M_PI) + 0.5 * logdet));
+        if (fphip_enum_gh_nodes(d_eff, rd.data(), pruning, std::min(rd[0], gh2)) > lim)
+          take[w] = 0;
+      }
+    }
+  }
+  const bool any_wave = std::find(take.begin(), take.end(), 1) != take.end();
+  const bool all_wave = std::find(take.begin(), take.end(), 0) == take.end();
+  if (any_wave)
+    if (int rc = svp_wave_run(g, first_lattice, count, pruning, all_wave ? nullptr : take.data(), sol_coord, vec, norm,
+                              nodes, status))
+      return rc;
+  const float wave_ms = g->last_ms;
+  const size_t dd = (size_t)d, nn = (size_t)g->P.n;
+  for (int w = 0; w < count; ++w)
+  {
+    if (take[w])
+      continue;
+    if (gst[first_lattice + w] != 1)
+    {
+      memset(sol_coord + (size_t)w * dd, 0, dd * sizeof(int64_t));
+      memset(vec + (size_t)w * nn, 0, nn * sizeof(int64_t));
+      norm[w] = 0, nodes[w] = 0, status[w] = 0;
+      continue;
+    }
+    if (int rc = svp_enum_one(g, ectx, first_lattice + w, pruning, sol_coord + (size_t)w * dd, vec + (size_t)w * nn,
+                              norm + w, nodes + w, status + w))
+      return rc;
+  }
+  g->last_ms = wave_ms;
+  return FPHIP_OK;
+}
+
 // ---- lists of short / near vectors (list_vectors.hip; the enumeration: fphip_enum_list) ----------------------------
 // the vector kernel over m records of one lattice: vec [m][n], norm [m], status [m]
 static int list_vectors_run(fphip_gso *g, int lattice, uint64_t m, const int64_t *coef, const int64_t *target, int64_t *vec,

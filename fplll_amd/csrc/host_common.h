@@ -58,6 +58,8 @@ int fphip_ctx_device(fphip_ctx *ctx);
 int fphip_ctx_ensure_task_buffers(fphip_ctx *ctx);
 int fphip_ctx_set_task_cap(fphip_ctx *ctx, unsigned cap);
 int fphip_ctx_allow_wide_target(fphip_ctx *ctx, int on);  // closest-vector calls above 64 rows
+// Gaussian-heuristic node estimate of a block (the sum over the levels of what places the phase cuts), d <= 256
+double fphip_enum_gh_nodes(int d, const double *rdiag, const double *pruning, double maxdist);
 
 static inline int fail(fphip_ctx *ctx, const char *what, hipError_t e)
 {

@@ -120,6 +120,21 @@ __global__ void cvp_babai_kernel(int T, int ldt, int d, int start, int dimension
                                  long long *w, int *status, double *wx);
 __global__ void list_vectors_kernel(ListVec P);  // list_vectors.hip
 
+// svp_wave.hip: the shortest-vector solver, one wave per lattice of the range [first, first + count)
+struct SvpWave
+{
+  int first, count;
+  int stack_doubles, mu_doubles;  // per wave, in LDS: the walk's column stack (d (d + 1) / 2 + 2), the mu triangle
+  const double *pruning;          // [d] or null (every coefficient 1)
+  const int *take;                // [count] or null: 0 = this lattice goes another route, its outputs are left alone
+  long long *sol_coord;           // [count][d]
+  long long *vec;                 // [count][n]
+  long long *norm;                // [count]
+  unsigned long long *nodes;      // [count] fplll's counting rule
+  int *status;                    // [count] 1 RED_SUCCESS, 0 update_gso failed, -2 beyond 63 bits (outputs zero)
+};
+template <int NQ> __global__ void svp_wave_kernel(GsoBatch P, SvpWave A);
+
 // lll_gram.hip
 template <int NQ> __global__ void lll_gram_kernel(GramBatch P, double delta, double eta, double logdelta, int siegel);
 template <int NQ> __global__ void gram_update_kernel(GramBatch P);

@@ -624,6 +624,39 @@ class MatGSOBatch:
         self._chk(rc, "closest_vector")
         return sol, dist, st
 
+    def shortest_vector(self, first=0, count=None, pruning=None, route="auto", ectx=None, method=0, flags=0):
+        """fphip_shortest_vector: shortest_vector(b, sol_coord, SVPM_FAST) for the lattices [first, first + count) of
+        the batch (LLL-reduced bases), decided on exact integer norms.  ``route``: "wave" (one wavefront per lattice,
+        one launch for the range, d <= 64, deterministic), "enum" (one enumerator call per lattice on ``ectx``; None:
+        this object's context) or "auto".  ``pruning``: [d] level coefficients or None.  Returns (sol_coord int64
+        [count][d], vec int64 [count][n], norm int64 [count], nodes uint64 [count], status int32 [count]: 1, 0 =
+        update_gso failed, -2 = beyond 63 bits — that lattice's outputs are zero)."""
+        if route not in _lib.SVP_ROUTES:
+            raise ValueError("shortest_vector: route is one of %s, got %r" % (", ".join(sorted(_lib.SVP_ROUTES)), route))
+        count = self.batch - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.batch:
+            raise ValueError("shortest_vector: lattices [%d, %d) outside the batch of %d" % (first, first + count, self.batch))
+        pr = None
+        if pruning is not None:
+            pr = np.ascontiguousarray(pruning, dtype=np.float64)
+            if pr.shape != (self.d,):
+                raise ValueError("shortest_vector: pruning is [%d], got shape %r" % (self.d, pr.shape))
+        sol = np.zeros((count, self.d), dtype=np.int64)
+        vec = np.zeros((count, self.n), dtype=np.int64)
+        norm = np.zeros(count, dtype=np.int64)
+        nodes = np.zeros(count, dtype=np.uint64)
+        st = np.zeros(count, dtype=np.int32)
+        _lib.bind_shortest_vector(self.lib)
+        rc = self.lib.fphip_shortest_vector(
+            self.h, None if ectx is None else ectx.handle, first, count, method, flags,
+            None if pr is None else pr.ctypes.data_as(ctypes.c_void_p), _lib.SVP_ROUTES[route],
+            *(a.ctypes.data_as(ctypes.c_void_p) for a in (sol, vec, norm, nodes, st)))
+        if rc == _lib.FPHIP_UNSUPPORTED:
+            from .enumeration import Unsupported
+            raise Unsupported("shortest_vector declined by the device layer (d=%d): %s" % (self.d, self.ctx.last_error()))
+        self._chk(rc, "shortest_vector")
+        return sol, vec, norm, nodes, st
+
     def records_to_vectors(self, coef, target=None, lattice=0):
         """fphip_list_records_to_vectors: for every row of ``coef`` (int64 [m][d]) the vector sum_i coef_i b_i (minus
         the int64 ``target`` [n] when given) and its exact squared norm.  Returns (vec int64 [m][n], norm int64 [m],

@@ -1,10 +1,14 @@
-"""Lists of short and near lattice vectors: every vector within a radius, exactly.
+"""Shortest vectors, and lists of short and near lattice vectors: every vector within a radius, exactly.
 
 What the reference does with a BEST_N evaluator that never fills (``FastEvaluator(999999)`` in its test_list_cvp; the
 list behind ``shortest_vectors(..., max_sols)``): kissing numbers, theta series, list decoding.  Everything is computed
 on the GPU behind ``fphip_list_vectors`` (include/fplll_hip.h): update_gso, a list enumeration that keeps every
 candidate on the device (``fphip_enum_list``), the vector kernel (exact int64 vectors and norms) and the filter on the
 exact integer norm; nothing here enumerates on the CPU.  Bases of at most 64 rows with int64 entries, one rank.
+
+``shortest_vector`` / ``shortest_vector_batch`` are the reference's ``shortest_vector(b, sol_coord, SVPM_FAST)``
+(``fplll -a svp``) behind ``fphip_shortest_vector``: a wave-per-lattice kernel for batches of bases of at most 64 rows,
+the multi-wave enumerator for larger ones, the answer decided on exact integer norms on either route.
 """
 import numpy as np
 
@@ -70,3 +74,49 @@ def theta_series(ctx, b, bound_sq, reduce=True, ectx=None):
         count, _, _, norm = short_vectors(ctx, b, bound_sq, reduce=reduce, cap=count, ectx=ectx)
     vals, cnts = np.unique(norm, return_counts=True)
     return {int(v): 2 * int(c) for v, c in zip(vals, cnts)}
+
+
+def shortest_vector_batch(ctx, bs, reduce=True, pruning=None, route="auto", ectx=None):
+    """A shortest non-zero vector of every lattice of ``bs`` (int64 [B][d][n], rows = basis vectors):
+    shortest_vector(b, sol_coord, SVPM_FAST) of the reference, one call for the batch.  ``reduce=True`` runs the batched
+    LLL first (the enumeration expects a reduced basis) and expresses ``sol_coord`` in the caller's basis through u, in
+    exact Python integers.  ``pruning``: [d] level coefficients or None; ``route``: "auto", "wave" (one wavefront per
+    lattice, d <= 64, deterministic) or "enum" (one enumerator call per lattice, on ``ectx``).  Returns ``(sol_coord
+    [B][d], vec int64 [B][n], norm int64 [B])`` with vec = sol_coord b and norm = |vec|^2 exactly; ``sol_coord`` is
+    int64 without ``reduce`` and an object array of Python integers with it.  Raises ``HipError`` naming the lattice
+    where a status is not RED_SUCCESS."""
+    b = np.ascontiguousarray(bs, dtype=np.int64)
+    if b.ndim != 3 or b.shape[0] < 1 or b.shape[1] < 1 or b.shape[1] > b.shape[2]:
+        raise ValueError("shortest_vector_batch: bs is [B][d][n] with B >= 1 and 1 <= d <= n, got shape %r" % (b.shape,))
+    if route not in _lib.SVP_ROUTES:
+        raise ValueError("shortest_vector_batch: route is one of %s, got %r" % (", ".join(sorted(_lib.SVP_ROUTES)), route))
+    if pruning is not None and np.shape(pruning) != (b.shape[1],):
+        raise ValueError("shortest_vector_batch: pruning is [%d], got shape %r" % (b.shape[1], np.shape(pruning)))
+    g = MatGSOBatch(ctx, b.shape[0], b.shape[1], b.shape[2])
+    try:
+        g.set_basis(b)
+        u = None
+        if reduce:
+            g.enable_transform()
+            status, _ = g.lll()
+            for k, s in enumerate(status):
+                if s != RED_SUCCESS:
+                    raise _lib.HipError("shortest_vector: lll of lattice %d ended with status %d" % (k, s))
+            u = g.get_transform()
+        sol, vec, norm, _, status = g.shortest_vector(pruning=pruning, route=route, ectx=ectx)
+    finally:
+        g.close()
+    for k, s in enumerate(status):
+        if s != RED_SUCCESS:
+            raise _lib.HipError("shortest_vector: lattice %d ended with status %d (%s)" % (
+                k, s, "an entry or a norm beyond 63 bits" if s == -2 else "update_gso failed"))
+    if u is not None:  # v = sol (u b_in): the coefficients in the caller's basis, exact
+        sol = np.stack([sol[k].astype(object).dot(u[k].astype(object)) for k in range(len(sol))])
+    return sol, vec, norm
+
+
+def shortest_vector(ctx, b, reduce=True, pruning=None, route="auto", ectx=None):
+    """``shortest_vector_batch`` for one basis ``b`` (int64 [d][n]): ``(sol_coord [d], vec [n], norm)``."""
+    b = _basis(b, "shortest_vector")
+    sol, vec, norm = shortest_vector_batch(ctx, b[None], reduce=reduce, pruning=pruning, route=route, ectx=ectx)
+    return sol[0], vec[0], int(norm[0])

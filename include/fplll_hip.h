@@ -630,6 +630,45 @@ int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, const int64_t
 int fphip_list_records_to_vectors(fphip_gso *g, int lattice, uint64_t m, const int64_t *coef, const int64_t *target,
                                   int64_t *vec, int64_t *norm, int *status);
 
+/*
+ * Shortest vectors (ABI version 6).  fphip_shortest_vector: shortest_vector(b, sol_coord, SVPM_FAST)
+ * (svpcvp.cpp:84-241) for the lattices [first_lattice, first_lattice + count) of g, on LLL-reduced bases of int64
+ * entries.  It runs update_gso, then per lattice: the exact squared norm of every row; last_useful_index on the true
+ * r_ii (rows at and above it keep coefficient 0); the initial answer, the shortest row below that index (the lowest
+ * index on ties); an enumeration whose candidates are decided on EXACT integers — a candidate replaces the best only if
+ * its exact squared norm is strictly smaller, and the radius is then (double)(N_best - 1) (1 + 2^-30): squared norms
+ * are integers, so only a norm <= N_best - 1 can still improve the answer.  The 2^-30 is the margin of
+ * fphip_closest_vector and fphip_list_vectors: a heuristic allowance for the rounding of the enumeration's doubles, not
+ * a proved error bound (the reference enlarges its radius by get_max_error_aux there).
+ *   route  FPHIP_SVP_ROUTE_WAVE: one wavefront per lattice, the whole range in one launch (svp_wave.hip), d <= 64 —
+ *          more rows: FPHIP_UNSUPPORTED with a text.  The walk is sequential in the reference's order: the answer is
+ *          the first vector of minimal exact norm in depth-first order, and two calls give identical arrays.
+ *          FPHIP_SVP_ROUTE_ENUM: one fphip_enum_run per lattice on `ectx` (NULL: the context of g), primal, one rank,
+ *          d <= FPHIP_ENUM_MAX_DIM; the callback computes the candidate's norm in 128-bit integers on the host.  Which
+ *          of several vectors of the minimal norm is returned is unspecified (the walk is parallel); the norm is not.
+ *          FPHIP_SVP_ROUTE_AUTO: WAVE where d <= 64 and the Gaussian-heuristic node estimate of the lattice's tree
+ *          (radius min(r_00, GH^2), GH the Gaussian-heuristic length) is at most FPHIP_SVP_WAVE_MAX_NODES (environment; the built-in default: DESIGN section 3f),
+ *          ENUM otherwise.
+ *   pruning [d] or NULL: the level bound is pruning[k] * radius (shortest_vector_pruning's one vector).
+ *   outputs, per lattice of the range: sol_coord [count][d], vec [count][n] (sum_i sol_coord_i b_i), norm [count]
+ *          (|vec|^2, exact), nodes [count] (fplll's counting rule; 0 where nothing was enumerated), status [count]:
+ *          1 RED_SUCCESS, 0 update_gso failed, -2 a row norm or a candidate left the 63-bit range (outputs zero).
+ * method: FPHIP_SVPM_FAST only — SVPM_PROVED (the exact evaluator) is declined; flags: 0 only — SVP_OVERRIDE_BND and
+ * SVP_DUAL are declined.  Every decline is FPHIP_UNSUPPORTED with a fphip_last_error text before anything is launched.
+ * Not offered: sub-solutions, auxiliary solutions, several ranks, entries beyond int64.
+ * fphip_gso_last_kernel_ms: the WAVE launch (0 when every lattice went the ENUM route).
+ */
+#define FPHIP_SVPM_FAST 0
+#define FPHIP_SVPM_PROVED 2
+#define FPHIP_SVP_OVERRIDE_BND 2
+#define FPHIP_SVP_DUAL 4
+#define FPHIP_SVP_ROUTE_AUTO 0
+#define FPHIP_SVP_ROUTE_WAVE 1
+#define FPHIP_SVP_ROUTE_ENUM 2
+int fphip_shortest_vector(fphip_gso *g, fphip_ctx *ectx, int first_lattice, int count, int method, int flags,
+                          const double *pruning, int route, int64_t *sol_coord, int64_t *vec, int64_t *norm,
+                          uint64_t *nodes, int *status);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Batched Householder R-factor: MatHouseholder<Z_NR<long>, FP_NR<double>> (householder.h:38)    */
 /*   fphip_hh_update_R = refresh_R_bf() + update_R() over all rows (householder.h:532-536,       */
