@@ -20,6 +20,11 @@
 // exponents of the device GSO first (get_mu_exp / get_r_exp: mu 2^(e_i - e_j), r 2^(2 e_i)) and floats the basis.
 // status: 1 ok; -2 a rounded coordinate, a coefficient or an entry of the running target left the 63-bit range (the
 // caller falls back); -1 the loop limit (the reference only warns, at 0x100 passes) — a lane never spins.
+// One more way out of the loop than the reference has: a pass whose x is exactly minus the x of the pass before would
+// bring back the target of two passes ago — the loop would alternate between two targets for ever, which is what a
+// target exactly halfway between two lattice points does to it (a tie rounds away from zero: 1/2 -> 1, then -1/2 -> -1;
+// the reference never returns from such a target).  Both targets are as near the origin as the loop brings them, so
+// the lane ends there, status 1, with the coefficients and the coordinates of this pass.
 //
 // cvp_babai_kernel is the nearest-plane loop alone on rows [start, start + dimension) with FP_NR<double>::rnd's rule
 // (rint: ties to even), one pass.
@@ -73,6 +78,7 @@ __global__ void __launch_bounds__(64) cvp_prepare_kernel(CvpPrep P)
   double *wx       = P.wx + t;
   long long *wt    = P.wt + t;
   long long *wk    = P.wk + t;
+  double *wp       = P.wp + t;
   int st           = 0;  // 0: still reducing
   if (mine)
   {
@@ -112,16 +118,18 @@ __global__ void __launch_bounds__(64) cvp_prepare_kernel(CvpPrep P)
       wx[i * ldt]    = c;
     }
     // babai
-    bool small = true;
+    bool small = true, undo = pass > 0;  // undo: x == -(the x of the pass before)
     for (int i = d - 1; i >= 0; --i)
     {
       const double xi = round(wx[i * ldt]);
       wx[i * ldt]     = xi;
       small           = small && (xi >= -1.0 && xi <= 1.0);
+      undo            = undo && xi == -wp[i * ldt];
+      wp[i * ldt]     = xi;
       for (int j = 0; j < i; ++j)
         wx[j * ldt] = wx[j * ldt] - P.mu[(size_t)i * d + j] * xi;
     }
-    if (small)
+    if (small || undo)
     {
       st = 1;
       continue;

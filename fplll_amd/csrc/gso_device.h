@@ -198,6 +198,7 @@ struct CvpPrep
   double *wx;     // [d][ldt] the nearest-plane vector
   long long *wt;  // [n][ldt] the running integer target
   long long *wk;  // [d][ldt] the accumulated coefficients
+  double *wp;     // [d][ldt] the nearest-plane vector of the pass before
 };
 
 // records of a list enumeration -> lattice vectors and exact norms (list_vectors.hip): one record per lane

@@ -2899,6 +2899,7 @@ static int cvp_prepare_run(fphip_gso *g, int lattice, int T, const int64_t *targ
   GCHK(B.get(&P.wx, d * ldt));
   GCHK(B.get(&P.wt, n * ldt));
   GCHK(B.get(&P.wk, d * ldt));
+  GCHK(B.get(&P.wp, d * ldt));
   GCHK(hipMemcpy(tg, targets, (size_t)T * n * sizeof(long long), hipMemcpyHostToDevice));
   GCHK(hipStreamSynchronize(nullptr));  // (see fphip_gso_set_basis)
   P.T = T, P.ldt = (int)ldt, P.d = (int)d, P.n = (int)n, P.ldn = g->P.ldn;
@@ -3557,7 +3558,24 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
   for (size_t i = 0; i < dd; ++i)
     for (size_t j = i + 1; j < dd; ++j)
       mut[i * dd + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
+  // a target far from the origin (a lattice point with large coefficients, or entries beyond 2^53, plus a small offset)
+  // loses the offset when its coordinates are formed in double: the closest-vector solver's preparation (the Babai loop
+  // in exact integers, cvp_prepare_kernel) moves it next to the origin first, and its coefficients are added back to
+  // every record.  A target that is near the origin already comes back unchanged (shift 0, the same coordinates).
+  std::vector<int64_t> shift(dd, 0);
+  bool prepared = false;
   if (target)
+  {
+    std::vector<double> ptc(dd);
+    std::vector<int64_t> pc(dd);
+    double pdesc = 0.0;
+    int pst      = 0;
+    if (int rc = cvp_prepare_run(g, lattice, 1, target, pc.data(), ptc.data(), &pdesc, &pst, nullptr, nullptr))
+      return rc;
+    if (pst == 1)
+      shift = pc, tc = ptc, prepared = true;
+  }
+  if (target && !prepared)
   {  // get_gscoords (svpcvp.cpp:494-515), the loops of cvp_prepare_kernel in its operand order
     for (size_t i = 0; i < dd; ++i)
     {
@@ -3601,7 +3619,10 @@ extern "C" int fphip_list_vectors(fphip_gso *g, fphip_ctx *ectx, int lattice, co
   {
     if (!(std::fabs(lx[i]) < 9223372036854775808.0))
       return fail_msg(g->ctx, "fphip_list_vectors: a coefficient beyond the int64 range");
-    rc_coef[i] = (int64_t)lx[i];
+    long long ci = 0;
+    if (__builtin_add_overflow((long long)lx[i], (long long)shift[i % dd], &ci))
+      return fail_msg(g->ctx, "fphip_list_vectors: a coefficient beyond the int64 range");
+    rc_coef[i] = ci;
   }
   if (int rc = list_vectors_run(g, lattice, found, rc_coef.data(), target, rvec.data(), rnorm.data(), rst.data()))
     return rc;

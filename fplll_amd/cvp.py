@@ -22,7 +22,8 @@ def closest_vectors(ctx, b, targets, reduce=False, method=CVPM_FAST, ectx=None, 
     ``ectx``: the context the enumerations run on (None: ``ctx``).
 
     Returns ``(sol_coord, vectors)`` — int64 [T][d] and the lattice vectors sol_coord @ b as Python-int object arrays
-    [T][n] — and with ``with_dist`` their squared distances to the targets as a third item.  A target whose numbers
+    [T][n] — and with ``with_dist`` the enumeration's squared distances as a third item (to the
+    target's projection on the span of ``b``: for d < n the part of the target orthogonal to the span is not in them).  A target whose numbers
     leave the int64 range raises ``HipError`` (the caller keeps the reference's multi-precision path)."""
     b = np.ascontiguousarray(b, dtype=np.int64)
     if b.ndim != 2:

@@ -582,7 +582,10 @@ double fphip_gso_last_kernel_ms(const fphip_gso *g);
  * these doubles are specified by tests/cvp_solver_cases.py (bit for bit), the solver's integer result by the
  * reference.  status [T]: 1 ok; -2 a coordinate, a coefficient or an entry of the running target left the 63-bit
  * range (the caller falls back; that target's outputs are zero); -1 no fixed point after 0x100 passes (where the
- * reference starts to warn, :573).  fphip_gso_last_kernel_ms: the preparation kernel.
+ * reference starts to warn, :573).  One exit the reference does not have: a pass whose rounded vector is exactly minus
+ * that of the pass before would only alternate between two targets (a target exactly halfway between two lattice
+ * points does that: ties round away from zero) — the loop ends there with status 1 and the values of that pass.
+ * fphip_gso_last_kernel_ms: the preparation kernel.
  *
  * fphip_gso_babai: MatGSOInterface::babai(w, v, start, dimension) (gso_interface.cpp:292-311) — the nearest-plane
  * loop alone, one pass, on the rows [start, start + dimension) (dimension -1: to the last row), rounding like
@@ -595,7 +598,8 @@ double fphip_gso_last_kernel_ms(const fphip_gso *g);
  * from the reference's sum of the r_ii (:601-606): the descent's leaf is the first the reference reaches and lies
  * inside either radius, so the closest vector is the same; where nothing lies inside the radius (or descent is 0:
  * the target is a lattice point) the answer is the descent itself.  sol_coord [T][d]; dist [T] (nullable): the
- * squared distance of the answer to the target.  status [T]: 1 RED_SUCCESS, or the preparation's -2 / -1
+ * enumeration's squared distance of the answer to the target's projection on the span of the basis (for d < n the
+ * part of the target orthogonal to the span, which no lattice point changes, is not in it).  status [T]: 1 RED_SUCCESS, or the preparation's -2 / -1
  * (sol_coord zero).  method: FPHIP_CVPM_FAST only; CVPM_PROVED (its max_indices reset path) and anything else return
  * FPHIP_UNSUPPORTED with a text.  Blocks the closest-vector enumeration declines (fphip_enum_run) are declined here
  * with its text. */
@@ -612,8 +616,9 @@ int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, cons
  * Lists of short / near vectors (ABI version 5).  fphip_list_vectors: the EXACT set of lattice
  * vectors v of one lattice with |v - target|^2 <= bound_sq (target NULL: around the origin, one of each pair +-v and no
  * zero vector), on an LLL-reduced basis of int64 entries, at most 64 rows (more: FPHIP_UNSUPPORTED), one rank.  It runs
- * update_gso; the true mu and r; with a target its Gram-Schmidt coordinates as fphip_cvp_prepare computes them (no
- * Babai reduction: the radius is the caller's); fphip_enum_list on `ectx` (NULL: g's context) at radius
+ * update_gso; the true mu and r; with a target fphip_cvp_prepare's Babai loop and Gram-Schmidt coordinates (a target
+ * far from the origin would lose a small offset from the lattice in double coordinates; the loop's coefficients are
+ * added back to every record; where the loop gives up, the coordinates of the target as it stands); fphip_enum_list on `ectx` (NULL: g's context) at radius
  * bound_sq (1 + 2^-30); the vector kernel (v = sum coef_i b_i - target and |v|^2 in int64 with overflow detection); and
  * the filter norm <= bound_sq on those exact integers — what decides a vector whose norm EQUALS the bound.  The 2^-30
  * is the margin of fphip_closest_vector: a heuristic allowance for the rounding of the enumeration's doubles, not a

@@ -121,6 +121,7 @@ def prepare(b, mu, rd, targets, max_passes=MAX_PASSES):
     tcoord = np.zeros((T, d))
     status = np.zeros(T, dtype=np.int32)
     passes = np.zeros(T, dtype=np.int32)
+    prev = {}  # target -> the x of its pass before
     for p in range(max_passes + 1):
         act = np.nonzero(status == 0)[0]
         if len(act) == 0:
@@ -148,7 +149,11 @@ def prepare(b, mu, rd, targets, max_passes=MAX_PASSES):
         with np.errstate(invalid="ignore"):
             small = np.all((x >= -1.0) & (x <= 1.0), axis=1)
         for a, t in enumerate(act):
-            if small[a]:
+            # a pass that would undo the one before (x == -x_before: the loop alternates between two targets, as on a
+            # target exactly halfway between two lattice points) ends the loop like a small x does
+            undo = t in prev and bool(np.all(x[a] == -prev[t]))
+            prev[t] = x[a].copy()
+            if small[a] or undo:
                 status[t] = 1
                 tcoord[t] = c[a]
                 continue

@@ -33,3 +33,12 @@ cat > $G/svp_rank_defect.json <<'JSON'
 {"desc": "the matrix of test_rank_defect (the reference's tests/test_svp.cpp): LLL-reduce, then shortest_vector must succeed",
  "basis": [[75, 44, -5, -16], [29, 7, -52, 134], [-89, 108, 56, 29], [-94, 55, -194, -20]]}
 JSON
+# The families of tests/solver_families.py (reduced in exact arithmetic, not by the reference): one knapsack, one
+# cut_rows and one scaled_root member, given to the driver as files; FAST and PROVED recorded as they come — on the
+# scaled root lattice the FAST method, which decides in floating point, returns a vector that is not the shortest.
+for name in knap_d20_b40 cut_scaled root_e8_s29_x2_0; do
+  t=$(mktemp)
+  python3 -c "import sys; sys.path.insert(0, 'tests'); import solver_families as F; print('[' + ' '.join('[' + ' '.join(str(v) for v in r) + ']' for r in F.basis('$name')) + ']')" > $t
+  $D --file $t > $G/svpsolve_fam_$name.json
+  rm -f $t
+done

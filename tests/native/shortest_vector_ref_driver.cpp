@@ -12,12 +12,18 @@
 //   shortest_vector_ref_driver d seed qbits
 //     a q-ary basis (ZZ_mat::gen_qary_prime(d / 2, qbits) under RandGen::init_with_seed(seed)), LLL-reduced by
 //     lll_reduction(LLL_DEF_DELTA, LLL_DEF_ETA, LM_WRAPPER), then shortest_vector with SVPM_FAST and with SVPM_PROVED.
+//   shortest_vector_ref_driver --file PATH
+//     the basis of PATH (fplll's matrix text, [[a b ...] [...]], d x n with d <= n) as it stands — no reduction: the
+//     families of tests/solver_families.py are reduced in exact arithmetic — then the same two calls.  Exit status 0
+//     whether or not the two norms agree (the test compares them).
 // Output (stdout): one JSON object — the reduced basis and per method the sol_coord shortest_vector returned, the
 // squared norm of sol_coord b (exact), the status and the time of the call on this machine's one core (milliseconds).
 // Exit status 3: the two methods' norms differ (the fixture script replaces such a seed).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <fstream>
 #include <vector>
 
 #include <fplll.h>
@@ -44,26 +50,45 @@ static void zlist(const std::vector<Z_NR<mpz_t>> &v)
 
 int main(int argc, char **argv)
 {
-  if (argc != 4)
+  const bool from_file = argc == 3 && !strcmp(argv[1], "--file");
+  if (argc != 4 && !from_file)
   {
-    fprintf(stderr, "usage: %s d seed qbits\n", argv[0]);
+    fprintf(stderr, "usage: %s d seed qbits | %s --file PATH\n", argv[0], argv[0]);
     return 2;
   }
-  const int d = atoi(argv[1]), seed = atoi(argv[2]), qbits = atoi(argv[3]);
-  RandGen::init_with_seed((unsigned long)seed);
-  ZZ_mat<mpz_t> A(d, d);
-  A.gen_qary_prime(d / 2, qbits);
-  int status = lll_reduction(A, LLL_DEF_DELTA, LLL_DEF_ETA, LM_WRAPPER, FT_DEFAULT, 0, LLL_DEFAULT);
+  int d = 0, n = 0, seed = 0, qbits = 0, status = RED_SUCCESS;
+  ZZ_mat<mpz_t> A;
+  if (from_file)
+  {
+    std::ifstream in(argv[2]);
+    if (!in || !(in >> A) || A.get_rows() < 1 || A.get_rows() > A.get_cols())
+    {
+      fprintf(stderr, "%s: no d x n matrix with d <= n\n", argv[2]);
+      return 2;
+    }
+    d = A.get_rows(), n = A.get_cols();
+  }
+  else
+  {
+    d = n = atoi(argv[1]), seed = atoi(argv[2]), qbits = atoi(argv[3]);
+    RandGen::init_with_seed((unsigned long)seed);
+    A.resize(d, d);
+    A.gen_qary_prime(d / 2, qbits);
+    status = lll_reduction(A, LLL_DEF_DELTA, LLL_DEF_ETA, LM_WRAPPER, FT_DEFAULT, 0, LLL_DEFAULT);
+  }
   if (status != RED_SUCCESS)
   {
     fprintf(stderr, "lll_reduction: %s\n", get_red_status_str(status));
     return 1;
   }
-  printf("{\"desc\":\"shortest_vector d=%d seed=%d qbits=%d\",\n\"d\":%d,\n\"n\":%d,\n\"basis\":[", d, seed, qbits, d, d);
+  if (from_file)
+    printf("{\"desc\":\"shortest_vector of a given %d x %d basis\",\n\"d\":%d,\n\"n\":%d,\n\"basis\":[", d, n, d, n);
+  else
+    printf("{\"desc\":\"shortest_vector d=%d seed=%d qbits=%d\",\n\"d\":%d,\n\"n\":%d,\n\"basis\":[", d, seed, qbits, d, d);
   for (int i = 0; i < d; ++i)
   {
-    std::vector<Z_NR<mpz_t>> row(d);
-    for (int j = 0; j < d; ++j)
+    std::vector<Z_NR<mpz_t>> row(n);
+    for (int j = 0; j < n; ++j)
       row[j] = A[i][j];
     printf("%s\n", i ? "," : "");
     zlist(row);
@@ -82,7 +107,7 @@ int main(int argc, char **argv)
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     Z_NR<mpz_t> acc, tmp;
     norms[m] = 0;
-    for (int j = 0; j < d; ++j)
+    for (int j = 0; j < n; ++j)
     {
       acc = 0;
       for (int i = 0; i < d && i < (int)sol.size(); ++i)
@@ -100,5 +125,5 @@ int main(int argc, char **argv)
     printf("}");
   }
   printf("}\n");
-  return norms[0] == norms[1] ? 0 : 3;
+  return from_file || norms[0] == norms[1] ? 0 : 3;
 }

@@ -149,7 +149,7 @@ def render(rows, out):
         else:
             how = "WAVE is slower per lattice at every dimension measured: the crossing lies below the estimate %.3g" % pts[0][0]
     fixtures = []
-    for p in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "svpsolve_*.json"))):
+    for p in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "svpsolve_q*.json"))):
         fx = json.load(open(p))
         fixtures.append((os.path.basename(p), fx["d"], fx["fast"]["ref_ms"], fx["proved"]["ref_ms"]))
     with open(out, "w") as f:

@@ -103,7 +103,7 @@ def test_model_takes_a_pruning_vector():
 
 
 # ---- 2. the fixtures --------------------------------------------------------------------------------------------------
-FIXTURES = sorted(glob.glob(os.path.join(C.GOLDEN, "svpsolve_*.json")))
+FIXTURES = sorted(glob.glob(os.path.join(C.GOLDEN, "svpsolve_q*.json")))
 
 
 def test_fixture_set():

@@ -17,7 +17,7 @@ import svp_model as M
 
 pytestmark = pytest.mark.gpu
 
-FIXTURES = {os.path.basename(p)[:-5]: json.load(open(p)) for p in sorted(glob.glob(os.path.join(C.GOLDEN, "svpsolve_*.json")))}
+FIXTURES = {os.path.basename(p)[:-5]: json.load(open(p)) for p in sorted(glob.glob(os.path.join(C.GOLDEN, "svpsolve_q*.json")))}
 _cache = {}
 
 
@@ -215,22 +215,34 @@ def test_degenerate_dimensions(ctx, d):
 @pytest.mark.parametrize("d", [63, 64])
 def test_lane_edge(ctx, d):
     """Rows up to lane 63, the answer b_{d-2} - b_{d-1} uses the last lane.  Catches: an off-by-one in the lane masks
-    (lane < k, readlane of level d - 1), the LDS triangle's size at d = 64."""
+    (lane < k, readlane of level d - 1), the LDS triangle's size at d = 64.  The norm is the exact minimum of the
+    lattice (tests/exact_lattice.py on the same basis): the model is not the only witness."""
+    import solver_families as F
     b = _steep(d)
+    assert b.tolist() == F.basis("steep_%d" % d)
     out, m = _wave_and_model(ctx, b)
     _same_as_model(out, m)
     assert m["d_eff"] == d and m["improvements"] >= 1 and m["sol_coord"][d - 1] != 0
     _check(b, out[0][0], out[1][0], out[2][0])
+    F.check_shortest("steep_%d" % d, out[0][0], out[1][0], out[2][0])
 
 
 @pytest.mark.parametrize("n", [64, 65, 130, 200])
 def test_every_width_class(ctx, n):
     """d = 16 with n = 64, 65, 130, 200 columns: one case per columns-per-lane class, three with a partial last column
-    group.  Catches: a column beyond n read or written, a norm that misses the last group."""
+    group.  Catches: a column beyond n read or written, a norm that misses the last group.  The norm is the exact
+    minimum of the first d_eff rows (rational enumeration, tests/exact_lattice.py) and sol_coord one of its minimal
+    vectors."""
+    import exact_lattice as X
     b = _reduced(ctx, 16, n, 0)
     out, m = _wave_and_model(ctx, b)
     _same_as_model(out, m)
     _check(b, out[0][0], out[1][0], out[2][0])
+    de = X.d_eff_exact(b.tolist())
+    lam1, xs, _ = X.lambda1_exact(b.tolist(), rows=de, max_nodes=200000)
+    assert m["d_eff"] == de and int(out[2][0]) == lam1
+    sol = tuple(_ints(out[0][0]))
+    assert not any(sol[de:]) and (sol[:de] in xs or tuple(-v for v in sol[:de]) in xs)
 
 
 def test_pruned_walk(ctx):
