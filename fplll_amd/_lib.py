@@ -120,6 +120,21 @@ def bind_shortest_vector(lib):
     return lib.fphip_shortest_vector
 
 
+# fphip_closest_vector_ex: the routes, and the status of a walk its node budget ended (WAVE route only)
+CVP_ROUTES = {"auto": 0, "wave": 1, "enum": 2}
+CVP_NODE_LIMIT = 2
+
+
+def bind_closest_vector_ex(lib):
+    """Prototype of fphip_closest_vector_ex (g, ectx, lattice, T, targets, method, route, max_nodes, sol_coord, dist,
+    norm, nodes, status)."""
+    vp = ctypes.c_void_p
+    lib.fphip_closest_vector_ex.restype = ctypes.c_int
+    lib.fphip_closest_vector_ex.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_uint64] + [vp] * 5
+    return lib.fphip_closest_vector_ex
+
+
 class HipError(RuntimeError):
     pass
 

@@ -2876,14 +2876,13 @@ static int cvp_unscale(fphip_gso *g, int lattice, CvpBufs &B, double **bfd, doub
   return FPHIP_OK;
 }
 
-// the preparation over T targets; mu_h / rd_h (nullable): the true mu [d][d] and r_ii [d] the kernel used
-static int cvp_prepare_run(fphip_gso *g, int lattice, int T, const int64_t *targets, int64_t *coef, double *target_coord,
-                           double *descent, int *status, double *mu_h, double *rd_h)
+// the preparation over T targets, its results left on the device in blocks of B: P's outputs, the targets, the true
+// mu [d][d] and r_ii [d] the kernel used
+static int cvp_prepare_dev(fphip_gso *g, int lattice, int T, const int64_t *targets, CvpBufs &B, CvpPrep &P,
+                           long long **tg_out, double **mu_out, double **rd_out)
 {
   const size_t d = g->P.d, n = g->P.n, ldt = ((size_t)T + 63) / 64 * 64;
-  hipStream_t s = fphip_ctx_stream(g->ctx);
-  CvpBufs B(s);
-  CvpPrep P;
+  hipStream_t s = B.s;
   memset(&P, 0, sizeof P);
   double *bfd = nullptr, *mu = nullptr, *rd = nullptr;
   if (int rc = cvp_unscale(g, lattice, B, &bfd, &mu, &rd))
@@ -2912,6 +2911,26 @@ static int cvp_prepare_run(fphip_gso *g, int lattice, int T, const int64_t *targ
   GCHK(hipEventRecord(g->ev[1], s));
   GCHK(hipStreamSynchronize(s));
   GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  *tg_out = tg, *mu_out = mu, *rd_out = rd;
+  return FPHIP_OK;
+}
+
+// the preparation over T targets; mu_h / rd_h (nullable): the true mu [d][d] and r_ii [d] the kernel used
+static int cvp_prepare_run(fphip_gso *g, int lattice, int T, const int64_t *targets, int64_t *coef, double *target_coord,
+                           double *descent, int *status, double *mu_h, double *rd_h, CvpBufs *keep = nullptr,
+                           CvpPrep *P_out = nullptr, long long **tg_out = nullptr, double **mu_out = nullptr,
+                           double **rd_out = nullptr)
+{
+  const size_t d = g->P.d;
+  CvpBufs own(fphip_ctx_stream(g->ctx));
+  CvpBufs &B = keep ? *keep : own;  // (keep: the caller goes on with the device blocks)
+  CvpPrep P;
+  long long *tg = nullptr;
+  double *mu = nullptr, *rd = nullptr;
+  if (int rc = cvp_prepare_dev(g, lattice, T, targets, B, P, &tg, &mu, &rd))
+    return rc;
+  if (P_out)
+    *P_out = P, *tg_out = tg, *mu_out = mu, *rd_out = rd;
   GCHK(hipMemcpy(coef, P.coef, (size_t)T * d * sizeof(long long), hipMemcpyDeviceToHost));
   GCHK(hipMemcpy(target_coord, P.tcoord, (size_t)T * d * sizeof(double), hipMemcpyDeviceToHost));
   GCHK(hipMemcpy(descent, P.descent, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
@@ -2997,7 +3016,149 @@ double cvp_best_cb(void *user, double dist, const double *sol)
   }
   return b->dist;
 }
+
+// The default of FPHIP_CVP_WAVE_NODES_PER_TARGET: c, the number of nodes a lone wave of cvp_wave_kernel walks in the
+// wall time of one ENUM-route call.  The AUTO route's budget per target is c min(T, resident waves of the launch), so
+// that its wave stage never lasts longer than the ENUM route would have taken for the same batch.  Measured
+// (tests/perf/cvp_wave_bench.py): a lone wave walks 2.91e6 nodes/s (the 1.2e6-node near:10 target of cvpsolve_q36); one
+// ENUM call took 0.196 ms per target on the 24-row basis (trees of about a hundred nodes: the call's floor) and 6.15 ms
+// on the 40-row basis with the bench's targets (trees of about 6e5 nodes).  c is the product with the SMALLER time,
+// 2.91e6 x 0.196e-3 = 571, so that the bound holds on both; with the 40-row time it would be 17 900.  The session
+// recorded in profiles/cvp_wave.md (the same code with this default) gives 526 and 21 100: within the box noise.
+constexpr double CVP_WAVE_NODES_PER_TARGET_DEFAULT = 570.0;
+
+// |target - sum sol_i b_i|^2 on the host in 128-bit integers; false: it leaves the int64 range
+bool cvp_host_norm(int d, int n, const long long *b, const int64_t *target, const int64_t *sol, long long *out)
+{
+  __int128 nrm = 0;
+  for (int j = 0; j < n; ++j)
+  {
+    __int128 w = (__int128)target[j];
+    for (int i = 0; i < d; ++i)
+    {
+      __int128 p, q;  // (a product is below 2^126)
+      if (sol[i] == 0)
+        continue;
+      p = (__int128)sol[i] * (__int128)b[(size_t)i * n + j];
+      if (__builtin_sub_overflow(w, p, &q))
+        return false;
+      w = q;
+    }
+    __int128 p, q;
+    if (__builtin_mul_overflow(w, w, &p) || __builtin_add_overflow(nrm, p, &q))
+      return false;
+    nrm = q;
+  }
+  if (nrm > (__int128)std::numeric_limits<long long>::max())
+    return false;
+  *out = (long long)nrm;
+  return true;
+}
+
+// the AUTO route's second stage: the evaluator of cvp_wave.hip on the host, the candidate's exact squared distance to
+// the reduced target in 128-bit integers.  Only a strictly smaller N replaces the best the wave stage left.
+struct CvpExact
+{
+  int d, n;
+  const long long *b;       // [d][n] host copy of the rows
+  const int64_t *target;    // [n] the original target
+  const int64_t *coef;      // [d] the preparation's coefficients
+  bool have;                // nbest is known
+  bool improved, overflow;
+  long long nbest;
+  double radius, dist;
+  std::vector<double> x;
+  std::vector<int64_t> sol;
+};
+double cvp_exact_cb(void *user, double dist, const double *sol)
+{
+  CvpExact *B = (CvpExact *)user;
+  for (int i = 0; i < B->d; ++i)
+  {
+    long long xi;
+    if (!(std::fabs(sol[i]) < 9223372036854775808.0) ||
+        __builtin_add_overflow((long long)B->coef[i], (long long)sol[i], &xi))
+    {
+      B->overflow = true;
+      return 0.0;  // stop
+    }
+    B->sol[i] = xi;
+  }
+  long long nv = 0;
+  if (!cvp_host_norm(B->d, B->n, B->b, B->target, B->sol.data(), &nv))
+  {
+    B->overflow = true;
+    return 0.0;
+  }
+  if (!B->have || nv < B->nbest)
+  {
+    B->have = B->improved = true;
+    B->nbest = nv;
+    B->dist  = dist;
+    B->x.assign(sol, sol + B->d);
+    const double r2 = dist + dist * 0x1p-30;
+    B->radius       = r2 < B->radius ? r2 : B->radius;
+    if (nv == 0)
+      return 0.0;  // nothing is closer
+  }
+  return B->radius;
+}
 }  // namespace
+
+// the launch geometry of cvp_wave_kernel for T targets: four waves per workgroup (one per SIMD of a compute unit, the
+// mu triangle shared between them), as many workgroups per compute unit as the occupancy query allows
+static int cvp_wave_geometry(fphip_gso *g, int T, CvpWave &A, int *wpb_out, int *grid_out, size_t *lds_out)
+{
+  const size_t d = g->P.d, n = g->P.n;
+  const int nq = (int)((std::max(d, n) + 63) / 64), wpb = 4;
+  A.stack_doubles  = (int)(d * (d + 1) / 2 + 2);
+  A.mu_doubles     = (int)std::max<size_t>(d * (d - 1) / 2, 2);
+  const size_t lds = ((size_t)A.mu_doubles + (size_t)A.stack_doubles * wpb) * sizeof(double);  // d = 64: 82 752 bytes
+  if (lds > 64 * 1024)
+    GCHK(dispatch_nq(nq, [&](auto NQ) { return allow_lds(cvp_wave_kernel<NQ>, lds); }));
+  int bpc = 0;
+  if (dispatch_nq(nq, [&](auto NQ) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, cvp_wave_kernel<NQ>, wpb * 64, lds);
+      }) != hipSuccess || bpc < 1)
+  {
+    (void)hipGetLastError();
+    bpc = std::max(1, std::min((int)((160 * 1024) / lds), 16 / wpb));
+  }
+  int grid = (T + wpb - 1) / wpb;
+  int cap  = fphip_ctx_num_cus(g->ctx) * bpc;
+  if (const char *e = getenv("FPHIP_CVP_WAVE_GRID"))  // (tests: a small grid makes a small batch go round the grid-stride loop)
+    cap = std::max(1, atoi(e));
+  *wpb_out = wpb, *grid_out = std::min(grid, cap), *lds_out = lds;
+  return FPHIP_OK;
+}
+
+// the wave-per-target kernel over the prepared targets (device blocks of the preparation); x [T][d], found [T]
+static int cvp_wave_run(fphip_gso *g, CvpBufs &B, CvpWave A, int wpb, int grid, size_t lds, int64_t *x, double *dist,
+                        int64_t *norm, uint64_t *nodes, int *found, int *status)
+{
+  const size_t d = g->P.d, n = g->P.n, T = (size_t)A.T;
+  const int nq   = (int)((std::max(d, n) + 63) / 64);
+  hipStream_t s  = B.s;
+  GCHK(B.get(&A.x, T * d));
+  GCHK(B.get(&A.dist, T));
+  GCHK(B.get(&A.norm, T));
+  GCHK(B.get(&A.nodes, T));
+  GCHK(B.get(&A.found, T));
+  GCHK(B.get(&A.status, T));
+  GCHK(hipEventRecord(g->ev[0], s));
+  dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(cvp_wave_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, A); });
+  GCHK(hipGetLastError());
+  GCHK(hipEventRecord(g->ev[1], s));
+  GCHK(hipStreamSynchronize(s));
+  GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  GCHK(hipMemcpy(x, A.x, T * d * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(dist, A.dist, T * sizeof(double), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(norm, A.norm, T * sizeof(long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(nodes, A.nodes, T * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(found, A.found, T * sizeof(int), hipMemcpyDeviceToHost));
+  GCHK(hipMemcpy(status, A.status, T * sizeof(int), hipMemcpyDeviceToHost));
+  return FPHIP_OK;
+}
 
 // closest_vector(b, int_target, sol_coord, CVPM_FAST) (svpcvp.cpp:532-659) for T targets against one lattice:
 // update_gso, the preparation kernel over all targets, one closest-vector enumeration per target on ectx under a
@@ -3006,8 +3167,12 @@ double cvp_best_cb(void *user, double dist, const double *sol)
 // one the reference reaches and lies inside either radius, so the closest vector is the same, and the top of the
 // parallel walk runs under the INITIAL radius.  Nothing inside the radius (the descent's own leaf can miss it by the
 // rounding of another operand order): the answer is the descent.
-extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets, int method,
-                                    int64_t *sol_coord, double *dist, int *status)
+//
+// The routes: ENUM is the above; WAVE hands the prepared targets to cvp_wave_kernel in one launch;
+// AUTO runs the wave kernel under a budget and finishes the targets that reached it by one enumeration each.
+extern "C" int fphip_closest_vector_ex(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets,
+                                       int method, int route, uint64_t max_nodes, int64_t *sol_coord, double *dist,
+                                       int64_t *norm, uint64_t *nodes_out, int *status)
 {
   FPHIP_RANGE("fphip_closest_vector");
   if (!g || !targets || !sol_coord || !status)
@@ -3022,67 +3187,154 @@ extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, 
              "path, or an unknown one) is not offered: CVPM_FAST only", method);
     return FPHIP_UNSUPPORTED;
   }
-  const int d = g->P.d;
+  if (route != FPHIP_CVP_ROUTE_AUTO && route != FPHIP_CVP_ROUTE_WAVE && route != FPHIP_CVP_ROUTE_ENUM)
+    return fail_msg(g->ctx, "fphip_closest_vector: unknown route");
+  const int d = g->P.d, n = g->P.n;
+  if (route == FPHIP_CVP_ROUTE_WAVE && (d > 64 || n > 256))
+  {
+    snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: the WAVE route takes at most 64 rows and 256 columns "
+             "(d = %d, n = %d): use the ENUM route", d, n);
+    return FPHIP_UNSUPPORTED;
+  }
   if (d > FPHIP_ENUM_MAX_DIM)
   {
     snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: more than %d rows", FPHIP_ENUM_MAX_DIM);
     return FPHIP_UNSUPPORTED;
   }
+  const bool wave = route == FPHIP_CVP_ROUTE_WAVE || (route == FPHIP_CVP_ROUTE_AUTO && d <= 64 && n <= 256);
+  const bool auto_route = route == FPHIP_CVP_ROUTE_AUTO;
   std::vector<int> gst(g->P.batch, 0);
   if (int rc = fphip_gso_update(g, gst.data()))
     return rc;
   if (gst[lattice] != 1)
     return fail_msg(g->ctx, "fphip_closest_vector: update_gso failed (non-finite mu: RED_GSO_FAILURE)");
-  const size_t dd = (size_t)d;
+  const size_t dd = (size_t)d, nn = (size_t)n;
   std::vector<int64_t> coef((size_t)T * dd);
   std::vector<double> tc((size_t)T * dd), desc((size_t)T), mu(dd * dd), rd(dd), mut(dd * dd, 0.0), xr(dd);
   std::vector<int> pst((size_t)T);
-  if (int rc = cvp_prepare_run(g, lattice, T, targets, coef.data(), tc.data(), desc.data(), pst.data(), mu.data(), rd.data()))
+  CvpBufs B(fphip_ctx_stream(g->ctx));  // (the preparation's device blocks: the wave kernel reads them)
+  CvpPrep Pd;
+  long long *tg_d = nullptr;
+  double *mu_d = nullptr, *rd_d = nullptr;
+  if (int rc = cvp_prepare_run(g, lattice, T, targets, coef.data(), tc.data(), desc.data(), pst.data(), mu.data(), rd.data(),
+                               &B, &Pd, &tg_d, &mu_d, &rd_d))
     return rc;
-  const float prep_ms = g->last_ms;
+  float kernel_ms = g->last_ms;
   for (size_t i = 0; i < dd; ++i)
     for (size_t j = i + 1; j < dd; ++j)
       mut[i * dd + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
-  std::vector<uint64_t> nodes(dd + 1);
+  // the rows on the host, for the exact distances computed here
+  std::vector<long long> bh;
+  if (norm || auto_route)
+  {
+    bh.resize(dd * nn);
+    GCHK(hipMemcpy2D(bh.data(), nn * 8, g->P.b + (size_t)lattice * dd * g->P.ldn, (size_t)g->P.ldn * 8, nn * 8, dd,
+                     hipMemcpyDeviceToHost));
+  }
+  // ---- the wave stage: every target in one launch ---------------------------------------------------------------
+  std::vector<int64_t> wx, wnorm;
+  std::vector<double> wdist;
+  std::vector<uint64_t> wnodes;
+  std::vector<int> wfound, wst;
+  if (wave)
+  {
+    CvpWave A;
+    memset(&A, 0, sizeof A);
+    A.lattice = lattice, A.T = T;
+    A.coef = Pd.coef, A.tcoord = Pd.tcoord, A.descent = Pd.descent, A.pstatus = Pd.status;
+    A.targets = tg_d, A.mu = mu_d, A.rd = rd_d;
+    int wpb = 0, grid = 0;
+    size_t lds = 0;
+    if (int rc = cvp_wave_geometry(g, T, A, &wpb, &grid, &lds))
+      return rc;
+    A.max_nodes = max_nodes;
+    if (auto_route && max_nodes == 0)
+    {
+      const char *e  = getenv("FPHIP_CVP_WAVE_NODES_PER_TARGET");
+      const double c = e ? atof(e) : CVP_WAVE_NODES_PER_TARGET_DEFAULT;
+      const double v = std::floor(c * (double)std::min(T, grid * wpb));
+      A.max_nodes    = v >= 1.0 ? (v < 1.8e19 ? (unsigned long long)v : ~0ull) : 1ull;
+    }
+    wx.resize((size_t)T * dd), wnorm.resize((size_t)T), wdist.resize((size_t)T), wnodes.resize((size_t)T);
+    wfound.resize((size_t)T), wst.resize((size_t)T);
+    if (int rc = cvp_wave_run(g, B, A, wpb, grid, lds, wx.data(), wdist.data(), wnorm.data(), wnodes.data(),
+                              wfound.data(), wst.data()))
+      return rc;
+    kernel_ms = g->last_ms;
+  }
+  std::vector<uint64_t> nodes(FPHIP_ENUM_MAX_DIM + 1);
+  // one closest-vector enumeration of target t on ectx at radius^2 maxdist
+  auto enum_one = [&](int t, double maxdist, fphip_sol_cb cb, void *user, uint64_t *total) -> int
+  {
+    fphip_enum_opts o;
+    memset(&o, 0, sizeof o);
+    o.shard_count     = 1;
+    o.exchange_chunks = 1;
+    o.target          = tc.data() + (size_t)t * dd;
+    std::fill(nodes.begin(), nodes.end(), 0);
+    // (blocks above 64 rows: the enumerator's closest-vector mode takes them on request only; the solver asks)
+    const int wide_was = fphip_ctx_allow_wide_target(ectx, 1);
+    const int rc = fphip_enum_run(ectx, d, maxdist, mut.data(), rd.data(), nullptr, &o, cb, nullptr, user, nodes.data(),
+                                  nullptr);
+    fphip_ctx_allow_wide_target(ectx, wide_was);
+    if (rc != FPHIP_OK && ectx != g->ctx)
+      snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: enumeration of target %d: %s", t,
+               fphip_last_error(ectx));
+    for (int k = 0; k <= d; ++k)
+      *total += nodes[k];
+    return rc;
+  };
   for (int t = 0; t < T; ++t)
   {
     int64_t *out = sol_coord + (size_t)t * dd;
     memset(out, 0, dd * sizeof(int64_t));
     if (dist)
       dist[t] = 0.0;
+    if (norm)
+      norm[t] = 0;
+    if (nodes_out)
+      nodes_out[t] = 0;
     status[t] = pst[t];
     if (pst[t] != 1)
       continue;
     const double *c = tc.data() + (size_t)t * dd;
-    CvpBest best{d, false, 0.0, {}};
-    if (d >= 2 && desc[t] > 0.0)
+    const int64_t *tgt = targets + (size_t)t * nn, *cf = coef.data() + (size_t)t * dd;
+    bool have = false, norm_known = false;
+    double bd = desc[t];
+    long long nbest = 0;
+    uint64_t total = 0;
+    if (wave)
     {
-      fphip_enum_opts o;
-      memset(&o, 0, sizeof o);
-      o.shard_count     = 1;
-      o.exchange_chunks = 1;
-      o.target          = c;
-      const double maxdist = desc[t] + desc[t] * 0x1p-30;
-      // (blocks above 64 rows: the enumerator's closest-vector mode takes them on request only; the solver asks)
-      const int wide_was = fphip_ctx_allow_wide_target(ectx, 1);
-      const int rc = fphip_enum_run(ectx, d, maxdist, mut.data(), rd.data(), nullptr, &o, cvp_best_cb, nullptr, &best,
-                                    nodes.data(), nullptr);
-      fphip_ctx_allow_wide_target(ectx, wide_was);
-      if (rc != FPHIP_OK)
+      if (wst[t] == -2)
       {
-        if (ectx != g->ctx)
-          snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_closest_vector: enumeration of target %d: %s", t,
-                   fphip_last_error(ectx));
-        return rc;
+        status[t] = -2;
+        continue;
+      }
+      status[t] = wst[t];
+      total     = wnodes[t];
+      if (wfound[t])
+      {
+        have = norm_known = true;
+        for (size_t i = 0; i < dd; ++i)
+          xr[i] = (double)wx[(size_t)t * dd + i];
+        bd    = wdist[t];
+        nbest = wnorm[t];
       }
     }
-    double bd = desc[t];
-    if (best.have)
+    else
     {
-      xr = best.x;
-      bd = best.dist;
+      CvpBest best{d, false, 0.0, {}};
+      if (d >= 2 && desc[t] > 0.0)
+        if (int rc = enum_one(t, desc[t] + desc[t] * 0x1p-30, cvp_best_cb, &best, &total))
+          return rc;
+      if (best.have)
+      {
+        have = true;
+        xr   = best.x;
+        bd   = best.dist;
+      }
     }
-    else  // the descent itself (the same loop as the kernel's)
+    if (!have)  // the descent itself (the same loop as the kernel's)
       for (int k = d - 1; k >= 0; --k)
       {
         double newcenter = c[k];
@@ -3090,24 +3342,76 @@ extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, 
           newcenter -= xr[j] * mut[(size_t)k * dd + j];
         xr[k] = std::round(newcenter);
       }
+    if (wave && auto_route && status[t] == FPHIP_CVP_NODE_LIMIT)
+    {
+      // the second stage: one enumeration at the radius the wave stage reached, decided on exact integers
+      CvpExact ex{d, n, bh.data(), tgt, cf, norm_known, false, false, nbest, 0.0, bd, {}, std::vector<int64_t>(dd)};
+      if (!norm_known)
+      {  // (no candidate before the budget: the descent's point is the one to beat)
+        bool fits = true;
+        for (size_t i = 0; i < dd && fits; ++i)
+        {
+          long long xi = 0;
+          fits = std::fabs(xr[i]) < 9223372036854775808.0 && !__builtin_add_overflow((long long)cf[i], (long long)xr[i], &xi);
+          ex.sol[i] = xi;
+        }
+        ex.have = fits && cvp_host_norm(d, n, bh.data(), tgt, ex.sol.data(), &ex.nbest);
+      }
+      const double r0 = std::min(desc[t], bd);
+      ex.radius       = r0 + r0 * 0x1p-30;
+      if (!(ex.have && ex.nbest == 0))
+        if (int rc = enum_one(t, ex.radius, cvp_exact_cb, &ex, &total))
+          return rc;
+      if (ex.overflow)
+      {
+        status[t] = -2;
+        continue;
+      }
+      if (ex.improved)
+      {
+        xr = ex.x;
+        bd = ex.dist;
+      }
+      norm_known = ex.have;
+      nbest      = ex.nbest;
+      status[t]  = 1;
+    }
     for (size_t i = 0; i < dd; ++i)
     {
       long long xi = 0;
       if (!(std::fabs(xr[i]) < 9223372036854775808.0) ||
-          __builtin_add_overflow((long long)coef[(size_t)t * dd + i], (long long)xr[i], &xi))
+          __builtin_add_overflow((long long)cf[i], (long long)xr[i], &xi))
       {
         status[t] = -2;
         break;
       }
       out[i] = xi;
     }
-    if (status[t] != 1)
+    if (status[t] == -2)
+    {
       memset(out, 0, dd * sizeof(int64_t));
-    else if (dist)
+      continue;
+    }
+    if (dist)
       dist[t] = bd;
+    if (nodes_out)
+      nodes_out[t] = total;
+    if (norm)
+    {
+      if (!norm_known && !cvp_host_norm(d, n, bh.data(), tgt, out, &nbest))
+        nbest = 0;
+      norm[t] = nbest;
+    }
   }
-  g->last_ms = prep_ms;
+  g->last_ms = kernel_ms;
   return FPHIP_OK;
+}
+
+extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets, int method,
+                                    int64_t *sol_coord, double *dist, int *status)
+{
+  return fphip_closest_vector_ex(g, ectx, lattice, T, targets, method, FPHIP_CVP_ROUTE_ENUM, 0, sol_coord, dist, nullptr,
+                                 nullptr, status);
 }
 
 // ---- shortest vectors (svp_wave.hip; the ENUM route: fphip_enum_run) -----------------------------------------------

@@ -135,6 +135,28 @@ struct SvpWave
 };
 template <int NQ> __global__ void svp_wave_kernel(GsoBatch P, SvpWave A);
 
+// cvp_wave.hip: the closest-vector solver, one wave per target of ONE lattice; the inputs are the device outputs of
+// the preparation (CvpPrep) and the true mu / r_ii of cvp_unscale_kernel
+struct CvpWave
+{
+  int lattice, T;
+  int stack_doubles, mu_doubles;  // in LDS: per wave the walk's column stack (d (d + 1) / 2 + 2); per workgroup the mu triangle
+  unsigned long long max_nodes;   // 0: no budget
+  const long long *coef;          // [T][d]
+  const double *tcoord;           // [T][d]
+  const double *descent;          // [T]
+  const int *pstatus;             // [T] the preparation's status
+  const long long *targets;       // [T][n]
+  const double *mu, *rd;          // [d][d], [d]: the true values
+  long long *x;                   // [T][d] the best point's coefficients on the REDUCED target (the caller adds coef)
+  double *dist;                   // [T] its walk distance
+  long long *norm;                // [T] its exact squared distance
+  unsigned long long *nodes;      // [T] accepted (level, coefficient) pairs, leaves included
+  int *found;                     // [T] 0: not walked, or no candidate — the caller fills in the rounding descent
+  int *status;                    // [T] the preparation's, -2 beyond 63 bits, 2 the node budget ended the walk
+};
+template <int NQ> __global__ void cvp_wave_kernel(GsoBatch P, CvpWave A);
+
 // lll_gram.hip
 template <int NQ> __global__ void lll_gram_kernel(GramBatch P, double delta, double eta, double logdelta, int siegel);
 template <int NQ> __global__ void gram_update_kernel(GramBatch P);

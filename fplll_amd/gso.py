@@ -599,30 +599,39 @@ class MatGSOBatch:
                   "cvp_prepare")
         return coef, tc, desc, st
 
-    def closest_vector(self, targets, ectx=None, method=0, lattice=0):
-        """fphip_closest_vector: closest_vector(b, target, sol_coord, CVPM_FAST) for every row of ``targets`` (int64
-        [T][n]) against one lattice; ``ectx``: the enumeration context (None: this object's).  Returns
-        (sol_coord int64 [T][d], dist [T], status [T])."""
+    def closest_vector(self, targets, ectx=None, method=0, lattice=0, route="enum", max_nodes=0, full=False):
+        """fphip_closest_vector_ex: closest_vector(b, target, sol_coord, CVPM_FAST) for every row of ``targets`` (int64
+        [T][n]) against one lattice; ``ectx``: the enumeration context (None: this object's).  ``route``: "enum" (one
+        enumerator call per target, one after another), "wave" (one wavefront per target, all targets in one launch,
+        d <= 64 and n <= 256, decided on exact integers, deterministic; ``max_nodes`` > 0 is a node budget per target:
+        a walk that reaches it ends with status 2 and the best point so far) or "auto" (the wave kernel under a budget,
+        then one enumerator call for every target that reached it; never status 2).  Returns (sol_coord int64 [T][d],
+        dist [T], status [T]); with ``full`` also norm int64 [T] (the exact squared distance to the target; 0 where it
+        leaves int64) and nodes uint64 [T] after dist."""
+        if route not in _lib.CVP_ROUTES:
+            raise ValueError("closest_vector: route is one of %s, got %r" % (", ".join(sorted(_lib.CVP_ROUTES)), route))
+        if int(max_nodes) < 0:
+            raise ValueError("closest_vector: max_nodes is a node budget >= 0 (0: none), got %r" % (max_nodes,))
         t = np.ascontiguousarray(targets, dtype=np.int64)
         if t.ndim != 2 or t.shape[1] != self.n:
             raise ValueError("closest_vector: targets are [T][%d], got shape %r" % (self.n, t.shape))
         T = t.shape[0]
         sol = np.zeros((T, self.d), dtype=np.int64)
         dist = np.zeros(T, dtype=np.float64)
+        norm = np.zeros(T, dtype=np.int64)
+        nodes = np.zeros(T, dtype=np.uint64)
         st = np.zeros(T, dtype=np.int32)
-        fn = self.lib.fphip_closest_vector
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        fn = _lib.bind_closest_vector_ex(self.lib)
         rc = fn(self.h, None if ectx is None else ectx.handle, lattice, T, t.ctypes.data_as(ctypes.c_void_p), method,
-                sol.ctypes.data_as(ctypes.c_void_p), dist.ctypes.data_as(ctypes.c_void_p),
-                st.ctypes.data_as(ctypes.c_void_p))
+                _lib.CVP_ROUTES[route], int(max_nodes), sol.ctypes.data_as(ctypes.c_void_p),
+                dist.ctypes.data_as(ctypes.c_void_p), norm.ctypes.data_as(ctypes.c_void_p) if full else None,
+                nodes.ctypes.data_as(ctypes.c_void_p) if full else None, st.ctypes.data_as(ctypes.c_void_p))
         if rc == _lib.FPHIP_UNSUPPORTED:
             from .enumeration import Unsupported
             err = self.ctx.last_error()
             raise Unsupported("closest_vector declined by the device layer (d=%d): %s" % (self.d, err))
         self._chk(rc, "closest_vector")
-        return sol, dist, st
+        return (sol, dist, norm, nodes, st) if full else (sol, dist, st)
 
     def shortest_vector(self, first=0, count=None, pruning=None, route="auto", ectx=None, method=0, flags=0):
         """fphip_shortest_vector: shortest_vector(b, sol_coord, SVPM_FAST) for the lattices [first, first + count) of

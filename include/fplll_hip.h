@@ -613,6 +613,44 @@ int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, cons
                          int64_t *sol_coord, double *dist, int *status);
 
 /*
+ * Closest vectors, one wavefront per target (ABI version 7; csrc/cvp_wave.hip).
+ * fphip_closest_vector_ex is fphip_closest_vector with a route, a node budget and two more outputs;
+ * fphip_closest_vector is this call with FPHIP_CVP_ROUTE_ENUM and behaves as it always did.
+ *   route  FPHIP_CVP_ROUTE_ENUM: one enumerator call per target, one after another, as described above.
+ *          FPHIP_CVP_ROUTE_WAVE: after the preparation ALL targets go into one launch of cvp_wave_kernel, one wavefront
+ *          per target, d <= 64 and n <= 256 (more: FPHIP_UNSUPPORTED with a text, before anything is launched).  The
+ *          walk is the reference's depth-first walk with a target (every sibling by zig-zag, every leaf within the
+ *          radius a candidate, distance 0 included) on the true mu and r, no pruning; the decision is on EXACT integers:
+ *          N = |target - sum sol_coord_i b_i|^2 in int64.  The first candidate wins, a later one only with a strictly
+ *          smaller N; after a win at walk distance nd the radius is min(radius, nd (1 + 2^-30)); N = 0 ends the walk.
+ *          The initial radius is descent (1 + 2^-30), as in the ENUM route.  The answer is the first lattice point of
+ *          minimal exact distance in depth-first order, and two calls give identical arrays.  The 2^-30 is the heuristic
+ *          margin of the solvers: an allowance for the rounding of the walk's doubles, not a proved error bound.
+ *          max_nodes > 0 is a budget per target (accepted nodes, leaves included): a walk that reaches it stops with
+ *          status FPHIP_CVP_NODE_LIMIT and the best point so far in its outputs.  0: no budget.
+ *          FPHIP_CVP_ROUTE_AUTO: d > 64 or n > 256: ENUM.  Otherwise every target starts in the wave kernel under a
+ *          budget — max_nodes if non-zero, else c min(T, resident waves of the launch), c the built-in number of nodes
+ *          a lone wave walks in the time of one ENUM call (FPHIP_CVP_WAVE_NODES_PER_TARGET in the environment
+ *          overrides c; DESIGN section 3g has its derivation) — and those that end on the budget are finished by one
+ *          ENUM call each at radius min(descent, best nd) (1 + 2^-30), decided on 128-bit exact integers on the host:
+ *          only a strictly smaller N replaces the wave's best.  AUTO never returns FPHIP_CVP_NODE_LIMIT.
+ *   outputs  sol_coord [T][d]; dist [T] (nullable) as above; norm [T] (nullable): the exact squared distance of the
+ *          answer to the ORIGINAL target (in the ENUM route computed on the host afterwards; 0 where it leaves int64);
+ *          nodes [T] (nullable): nodes walked for the target, the sum of both stages in AUTO; status [T]: 1, the
+ *          preparation's -2 / -1, -2 where the reduced target or a candidate left the 63-bit range (outputs zero), or
+ *          FPHIP_CVP_NODE_LIMIT (WAVE only).
+ * FPHIP_CVP_WAVE_GRID (environment) caps the number of workgroups (tests: a small batch goes round the grid-stride
+ * loop).  fphip_gso_last_kernel_ms: the wave launch (the preparation kernel in the ENUM route).
+ */
+#define FPHIP_CVP_ROUTE_AUTO 0
+#define FPHIP_CVP_ROUTE_WAVE 1
+#define FPHIP_CVP_ROUTE_ENUM 2
+#define FPHIP_CVP_NODE_LIMIT 2
+int fphip_closest_vector_ex(fphip_gso *g, fphip_ctx *ectx, int lattice, int T, const int64_t *targets, int method,
+                            int route, uint64_t max_nodes, int64_t *sol_coord, double *dist, int64_t *norm,
+                            uint64_t *nodes, int *status);
+
+/*
  * Lists of short / near vectors (ABI version 5).  fphip_list_vectors: the EXACT set of lattice
  * vectors v of one lattice with |v - target|^2 <= bound_sq (target NULL: around the origin, one of each pair +-v and no
  * zero vector), on an LLL-reduced basis of int64 entries, at most 64 rows (more: FPHIP_UNSUPPORTED), one rank.  It runs
