@@ -9,5 +9,6 @@ from .enumeration import (  # noqa: F401
     EVALSTRATEGY_BEST_N_SOLUTIONS, EVALSTRATEGY_FIRST_N_SOLUTIONS,
     EVALSTRATEGY_OPPORTUNISTIC_N_SOLUTIONS, FastEvaluator, Unsupported, enumerate_block)
 from .cvp import closest_vector, closest_vectors  # noqa: F401
-from .svp import short_vectors, shortest_vector, shortest_vector_batch, theta_series, vectors_near  # noqa: F401
+from .svp import (short_vectors, shortest_vector, shortest_vector_batch, shortest_vectors,  # noqa: F401
+                  shortest_vectors_batch, theta_series, vectors_near)
 from .gram import MatGSOGramBatch, lll_reduction_gram  # noqa: F401

@@ -120,6 +120,15 @@ def bind_shortest_vector(lib):
     return lib.fphip_shortest_vector
 
 
+def bind_shortest_vectors(lib):
+    """Prototype of fphip_shortest_vectors (g, ectx, first_lattice, count, max_sols, bound_sq, method, flags, pruning,
+    route, found, sol_coord, vec, norm, nodes, status)."""
+    vp = ctypes.c_void_p
+    lib.fphip_shortest_vectors.restype = ctypes.c_int
+    lib.fphip_shortest_vectors.argtypes = [vp, vp] + [ctypes.c_int] * 3 + [vp] + [ctypes.c_int] * 2 + [vp, ctypes.c_int] + [vp] * 6
+    return lib.fphip_shortest_vectors
+
+
 # fphip_closest_vector_ex: the routes, and the status of a walk its node budget ended (WAVE route only)
 CVP_ROUTES = {"auto": 0, "wave": 1, "enum": 2}
 CVP_NODE_LIMIT = 2

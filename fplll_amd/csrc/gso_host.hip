@@ -3768,6 +3768,430 @@ extern "C" int fphip_shortest_vector(fphip_gso *g, fphip_ctx *ectx, int first_la
   return FPHIP_OK;
 }
 
+// ---- the N shortest vectors (svp_best.hip; the ENUM route: fphip_enum_run under a host table) ------------------------
+namespace
+{
+// the ENUM route's BEST_N evaluator: at most K records sorted by exact norm, ties in arrival order; the accept rule
+// and the radius are those of svp_best.hip
+struct SvpTable
+{
+  SvpBest cand;  // the exact candidate (d = the rows under enumeration)
+  int K;
+  long long B0;
+  std::vector<long long> norms;           // sorted
+  std::vector<std::vector<long long>> x;  // [found][d_eff]
+  double radius0() const { return (double)B0 * (1.0 + 0x1p-30); }
+  // the radius after a candidate: unchanged until the table is full, then (worst - 1) (1 + 2^-30); 0 = stop
+  double bound() const
+  {
+    if ((int)norms.size() < K)
+      return radius0();
+    return (double)(norms.back() - 1) * (1.0 + 0x1p-30);
+  }
+  void offer(long long nv, const double *sol)
+  {
+    const bool full = (int)norms.size() == K;
+    if (!(nv > 0 && nv <= B0 && (!full || nv < norms.back())))
+      return;
+    const size_t p = (size_t)(std::upper_bound(norms.begin(), norms.end(), nv) - norms.begin());
+    norms.insert(norms.begin() + p, nv);
+    std::vector<long long> xi((size_t)cand.d);
+    for (int i = 0; i < cand.d; ++i)
+      xi[i] = (long long)sol[i];
+    x.insert(x.begin() + p, xi);
+    if ((int)norms.size() > K)
+      norms.pop_back(), x.pop_back();
+  }
+};
+double svp_table_cb(void *user, double dist, const double *sol)
+{
+  (void)dist;  // (the decision is the integers')
+  SvpTable *T  = (SvpTable *)user;
+  long long nv = 0;
+  if (!svp_exact_candidate(&T->cand, sol, &nv))
+  {
+    T->cand.overflow = true;
+    return 0.0;  // stop
+  }
+  T->offer(nv, sol);
+  return T->bound();  // (0 once the table is full with worst = 1: nothing non-zero is shorter)
+}
+
+// the rows under enumeration: last_useful_index without a caller's bound; with one the threshold max(2 r_00, radius)
+int svp_best_rows(int d, const double *rd, bool has_bound, double radius0)
+{
+  if (!has_bound)
+    return svp_last_useful_index(d, rd);
+  const double thr = std::max(2.0 * rd[0], radius0);
+  int i;
+  for (i = d - 1; i > 0; --i)
+    if (rd[i] <= thr)
+      break;
+  return i + 1;
+}
+}  // namespace
+
+// the wave-per-lattice kernel over the range; outputs of the lattices with take_h[w] == 0 are left alone
+static int svp_best_wave_run(fphip_gso *g, int first, int count, int K, const int64_t *bound_sq, const double *pruning,
+                             const int *take_h, int *found, int64_t *sol_coord, int64_t *vec, int64_t *norm,
+                             uint64_t *nodes, int *status)
+{
+  const size_t d = g->P.d, n = g->P.n, kk = (size_t)K;
+  const int nq   = (int)((std::max(d, n) + 63) / 64);
+  int wpb        = 4;
+  SvpBestWave A;
+  memset(&A, 0, sizeof A);
+  A.first = first, A.count = count, A.max_sols = K;
+  A.stack_doubles = (int)(d * (d + 1) / 2 + 2);
+  A.mu_doubles    = (int)std::max<size_t>(d * (d - 1) / 2, 2);
+  const size_t per_wave = (size_t)(A.stack_doubles + A.mu_doubles) * sizeof(double);
+  const size_t lds      = per_wave * wpb;  // d <= 64: at most 131136 bytes
+  int bpc = (int)((160 * 1024) / lds);
+  if (bpc * wpb > 32)
+    bpc = 32 / wpb;
+  int grid = (count + wpb - 1) / wpb;
+  int cap  = fphip_ctx_num_cus(g->ctx) * std::max(bpc, 1);
+  if (const char *e = getenv("FPHIP_SVP_WAVE_GRID"))  // (tests: a small grid makes a small batch go round the grid-stride loop)
+    cap = std::max(1, atoi(e));
+  grid = std::min(grid, cap);
+  hipStream_t s = fphip_ctx_stream(g->ctx);
+  CvpBufs B(s);
+  double *pr_d = nullptr;
+  int *take_d  = nullptr;
+  long long *bound_d = nullptr;
+  GCHK(B.get(&A.rec, (size_t)count * kk * d));
+  GCHK(B.get(&A.sol_coord, (size_t)count * kk * d));
+  GCHK(B.get(&A.vec, (size_t)count * kk * n));
+  GCHK(B.get(&A.norm, (size_t)count * kk));
+  GCHK(B.get(&A.found, (size_t)count));
+  GCHK(B.get(&A.nodes, (size_t)count));
+  GCHK(B.get(&A.status, (size_t)count));
+  if (pruning)
+  {
+    GCHK(B.get(&pr_d, d));
+    GCHK(hipMemcpy(pr_d, pruning, d * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (take_h)
+  {
+    GCHK(B.get(&take_d, (size_t)count));
+    GCHK(hipMemcpy(take_d, take_h, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (bound_sq)
+  {
+    GCHK(B.get(&bound_d, (size_t)count));
+    GCHK(hipMemcpy(bound_d, bound_sq, (size_t)count * sizeof(long long), hipMemcpyHostToDevice));
+  }
+  GCHK(hipStreamSynchronize(nullptr));  // (see fphip_gso_set_basis)
+  A.pruning = pr_d;
+  A.take    = take_d;
+  A.bound   = bound_d;
+  if (lds > 64 * 1024)
+    GCHK(dispatch_nq(nq, [&](auto NQ) { return allow_lds(svp_best_kernel<NQ>, lds); }));
+  GCHK(hipEventRecord(g->ev[0], s));
+  dispatch_nq(nq, [&](auto NQ) { hipLaunchKernelGGL(svp_best_kernel<NQ>, dim3(grid), dim3(wpb * 64), lds, s, g->P, A); });
+  GCHK(hipGetLastError());
+  GCHK(hipEventRecord(g->ev[1], s));
+  GCHK(hipStreamSynchronize(s));
+  GCHK(hipEventElapsedTime(&g->last_ms, g->ev[0], g->ev[1]));
+  if (!take_h)
+  {  // the whole range: straight into the caller's arrays
+    GCHK(hipMemcpy(sol_coord, A.sol_coord, (size_t)count * kk * d * sizeof(long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(vec, A.vec, (size_t)count * kk * n * sizeof(long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(norm, A.norm, (size_t)count * kk * sizeof(long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(found, A.found, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(nodes, A.nodes, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(status, A.status, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return FPHIP_OK;
+  }
+  for (int w = 0; w < count; ++w)
+  {
+    if (!take_h[w])
+      continue;
+    GCHK(hipMemcpy(sol_coord + (size_t)w * kk * d, A.sol_coord + (size_t)w * kk * d, kk * d * sizeof(long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(vec + (size_t)w * kk * n, A.vec + (size_t)w * kk * n, kk * n * sizeof(long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(norm + (size_t)w * kk, A.norm + (size_t)w * kk, kk * sizeof(long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(found + w, A.found + w, sizeof(int), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(nodes + w, A.nodes + w, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(status + w, A.status + w, sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return FPHIP_OK;
+}
+
+// one lattice by the enumerator under the host table; outputs [K][d], [K][n], [K]
+static int svp_best_enum_one(fphip_gso *g, fphip_ctx *ectx, int lattice, int K, long long bound, const double *pruning,
+                             int *found, int64_t *sol, int64_t *vec, int64_t *norm, uint64_t *nodes, int *status)
+{
+  const int d = g->P.d, n = g->P.n;
+  const size_t dd = (size_t)d, nn = (size_t)n, kk = (size_t)K;
+  memset(sol, 0, kk * dd * sizeof(int64_t));
+  memset(vec, 0, kk * nn * sizeof(int64_t));
+  memset(norm, 0, kk * sizeof(int64_t));
+  *found = 0, *nodes = 0, *status = 1;
+  std::vector<double> mu(dd * dd), rd(dd);
+  std::vector<long long> bh(dd * nn);
+  {
+    hipStream_t s = fphip_ctx_stream(g->ctx);
+    CvpBufs B(s);
+    double *bfd_d = nullptr, *mu_d = nullptr, *rd_d = nullptr;
+    if (int rc = cvp_unscale(g, lattice, B, &bfd_d, &mu_d, &rd_d))
+      return rc;
+    GCHK(hipStreamSynchronize(s));
+    GCHK(hipMemcpy(mu.data(), mu_d, dd * dd * sizeof(double), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy(rd.data(), rd_d, dd * sizeof(double), hipMemcpyDeviceToHost));
+    GCHK(hipMemcpy2D(bh.data(), nn * 8, g->P.b + (size_t)lattice * dd * g->P.ldn, (size_t)g->P.ldn * 8, nn * 8, dd,
+                     hipMemcpyDeviceToHost));
+  }
+  std::vector<long long> rn(dd);
+  for (size_t i = 0; i < dd; ++i)
+  {
+    i128 acc = 0;
+    for (size_t j = 0; j < nn && acc <= (i128)std::numeric_limits<long long>::max(); ++j)
+      acc += (i128)bh[i * nn + j] * (i128)bh[i * nn + j];
+    if (acc > (i128)std::numeric_limits<long long>::max())
+    {
+      *status = -2;
+      return FPHIP_OK;
+    }
+    rn[i] = (long long)acc;
+  }
+  long long B0 = bound;
+  int d_eff;
+  if (bound > 0)
+    d_eff = svp_best_rows(d, rd.data(), true, (double)bound * (1.0 + 0x1p-30));
+  else
+  {
+    d_eff = svp_best_rows(d, rd.data(), false, 0.0);
+    B0    = *std::min_element(rn.begin(), rn.begin() + d_eff);
+  }
+  SvpTable T{SvpBest{d_eff, n, bh.data(), 0, false, {}, {}, std::vector<i128>(nn)}, K, B0, {}, {}};
+  if (T.radius0() > 0.0)
+  {
+    if (d_eff == 1)
+    {  // the multiples of b_0, as the walk steps through them: x = 1, 2, ... while the leaf is within the level bound
+      const double p0 = pruning ? pruning[0] : 1.0;
+      double radius   = T.radius0();
+      *nodes          = 1;  // (the leaf x = 0)
+      for (double x = 1.0;; x += 1.0)
+      {
+        if (!(x * x * rd[0] <= p0 * radius))
+          break;
+        ++*nodes;
+        radius = svp_table_cb(&T, 0.0, &x);
+        if (radius == 0.0)
+          break;
+      }
+    }
+    else
+    {
+      const size_t de = (size_t)d_eff;
+      std::vector<double> mut(de * de, 0.0);
+      for (size_t i = 0; i < de; ++i)
+        for (size_t j = i + 1; j < de; ++j)
+          mut[i * de + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
+      fphip_enum_opts o;
+      memset(&o, 0, sizeof o);
+      o.shard_count       = 1;
+      o.exchange_chunks   = 1;
+      o.min_nodes_decline = 0;  // never declined for being small
+      std::vector<uint64_t> nd(FPHIP_ENUM_MAX_DIM + 1, 0);
+      const int rc = fphip_enum_run(ectx, d_eff, T.radius0(), mut.data(), rd.data(), pruning, &o, svp_table_cb, nullptr, &T,
+                                    nd.data(), nullptr);
+      if (rc != FPHIP_OK)
+      {
+        if (ectx != g->ctx)
+          snprintf(fphip_ctx_errbuf(g->ctx), 512, "fphip_shortest_vectors: enumeration of lattice %d: %s", lattice,
+                   fphip_last_error(ectx));
+        return rc;
+      }
+      for (int k = 0; k <= d_eff; ++k)
+        *nodes += nd[k];
+    }
+  }
+  if (T.cand.overflow)
+  {
+    *status = -2;
+    *nodes  = 0;
+    return FPHIP_OK;
+  }
+  // ties in the coefficient order of fphip_list_vectors (from level d - 1 down): the arrival order is the parallel walk's
+  std::vector<size_t> ord(T.norms.size());
+  for (size_t i = 0; i < ord.size(); ++i)
+    ord[i] = i;
+  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
+    if (T.norms[a] != T.norms[b])
+      return T.norms[a] < T.norms[b];
+    for (size_t k = (size_t)d_eff; k-- > 0;)
+      if (T.x[a][k] != T.x[b][k])
+        return T.x[a][k] < T.x[b][k];
+    return a < b;
+  });
+  std::vector<double> xd((size_t)d_eff);
+  for (size_t o = 0; o < ord.size(); ++o)
+  {
+    const std::vector<long long> &xi = T.x[ord[o]];
+    for (int i = 0; i < d_eff; ++i)
+      sol[o * dd + i] = xi[i], xd[i] = (double)xi[i];
+    long long nv = 0;
+    svp_exact_candidate(&T.cand, xd.data(), &nv);  // (it fitted when it was offered; the coefficients came as doubles)
+    for (size_t j = 0; j < nn; ++j)
+      vec[o * nn + j] = (long long)T.cand.w[j];
+    norm[o] = T.norms[ord[o]];
+  }
+  *found = (int)ord.size();
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_shortest_vectors(fphip_gso *g, fphip_ctx *ectx, int first_lattice, int count, int max_sols,
+                                      const int64_t *bound_sq, int method, int flags, const double *pruning, int route,
+                                      int *found, int64_t *sol_coord, int64_t *vec, int64_t *norm, uint64_t *nodes,
+                                      int *status)
+{
+  FPHIP_RANGE("fphip_shortest_vectors");
+  if (!g)
+    return FPHIP_ERROR;
+  if (!found || !sol_coord || !vec || !norm || !nodes || !status)
+    return fail_msg(g->ctx, "fphip_shortest_vectors: found, sol_coord, vec, norm, nodes and status are all required");
+  if (!ectx)
+    ectx = g->ctx;
+  if (first_lattice < 0 || count <= 0 || first_lattice > g->P.batch - count)
+    return fail_msg(g->ctx, "fphip_shortest_vectors: lattices [first_lattice, first_lattice + count) outside the batch");
+  char *err = fphip_ctx_errbuf(g->ctx);
+  if (max_sols < 1 || max_sols > 64)
+  {
+    snprintf(err, 512, "fphip_shortest_vectors: max_sols = %d is outside 1 .. 64: for longer lists use short_vectors "
+             "(fphip_list_vectors), every vector within a radius", max_sols);
+    return FPHIP_ERROR;
+  }
+  bool any_bound = false;
+  if (bound_sq)
+    for (int w = 0; w < count; ++w)
+    {
+      if (bound_sq[w] < 0)
+        return fail_msg(g->ctx, "fphip_shortest_vectors: a negative bound_sq (0 = the default bound)");
+      any_bound = any_bound || bound_sq[w] > 0;
+    }
+  if (int rcg = session_guard(g, "fphip_shortest_vectors"))
+    return rcg;
+  if (method != FPHIP_SVPM_FAST)
+  {
+    snprintf(err, 512, "fphip_shortest_vectors: method %d (SVPM_PROVED and its exact evaluator, or an unknown one) is not "
+             "offered: SVPM_FAST only", method);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (flags != 0)
+  {
+    snprintf(err, 512, "fphip_shortest_vectors: flags 0x%x (SVP_DUAL, SVP_OVERRIDE_BND, or unknown ones) are not offered: "
+             "0 only", flags);
+    return FPHIP_UNSUPPORTED;
+  }
+  const int d = g->P.d, K = max_sols;
+  if (route != FPHIP_SVP_ROUTE_AUTO && route != FPHIP_SVP_ROUTE_WAVE && route != FPHIP_SVP_ROUTE_ENUM)
+    return fail_msg(g->ctx, "fphip_shortest_vectors: unknown route");
+  if (route == FPHIP_SVP_ROUTE_WAVE && d > 64)
+  {
+    snprintf(err, 512, "fphip_shortest_vectors: the WAVE route takes at most 64 rows (d = %d): use the ENUM route", d);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (d > FPHIP_ENUM_MAX_DIM)
+  {
+    snprintf(err, 512, "fphip_shortest_vectors: more than %d rows", FPHIP_ENUM_MAX_DIM);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (pruning)
+    for (int i = 0; i < d; ++i)
+      if (!(pruning[i] > 0.0) || !std::isfinite(pruning[i]))
+        return fail_msg(g->ctx, "fphip_shortest_vectors: a pruning coefficient that is not a positive finite number");
+  std::vector<int> gst(g->P.batch, 0);
+  if (int rc = fphip_gso_update(g, gst.data()))
+    return rc;
+  g->last_ms = 0.0f;
+  const size_t dd = (size_t)d, nn = (size_t)g->P.n, kk = (size_t)K;
+  // the route of every lattice of the range: 1 = WAVE
+  std::vector<int> take((size_t)count, route == FPHIP_SVP_ROUTE_ENUM || d > 64 ? 0 : 1);
+  if (route == FPHIP_SVP_ROUTE_AUTO && d <= 64)
+  {
+    const char *e    = getenv("FPHIP_SVP_WAVE_MAX_NODES");
+    const double lim = e ? atof(e) : SVP_WAVE_MAX_NODES_DEFAULT;
+    if (lim > 0.0)
+    {
+      const bool as_one = K == 1 && !any_bound;  // the decision of fphip_shortest_vector
+      std::vector<double> rs((size_t)count * dd);
+      std::vector<long long> es((size_t)count * dd), bh;
+      GCHK(hipMemcpy(rs.data(), g->P.rdg + (size_t)first_lattice * dd, rs.size() * sizeof(double), hipMemcpyDeviceToHost));
+      GCHK(hipMemcpy(es.data(), g->P.rexp + (size_t)first_lattice * dd, es.size() * sizeof(long long), hipMemcpyDeviceToHost));
+      std::vector<double> rd(dd);
+      for (int w = 0; w < count; ++w)
+      {
+        if (gst[first_lattice + w] != 1)
+          continue;  // (the kernel reports it)
+        for (size_t i = 0; i < dd; ++i)
+          rd[i] = std::ldexp(rs[(size_t)w * dd + i], g->P.row_expo ? (int)(2 * es[(size_t)w * dd + i]) : 0);
+        const long long bw = bound_sq ? bound_sq[w] : 0;
+        const int d_eff    = svp_best_rows(d, rd.data(), bw > 0, (double)bw * (1.0 + 0x1p-30));
+        bool pos = true;
+        for (int i = 0; i < d_eff; ++i)
+          pos = pos && rd[i] > 0.0 && std::isfinite(rd[i]);
+        if (!pos)
+          continue;
+        double radius;
+        if (as_one)
+        {
+          double logdet = 0.0;
+          for (int i = 0; i < d_eff; ++i)
+            logdet += std::log(rd[i]);
+          const double gh2 = std::exp((2.0 / d_eff) * (std::lgamma(0.5 * d_eff + 1.0) - 0.5 * d_eff * std::log(M_PI) + 0.5 * logdet));
+          radius = std::min(rd[0], gh2);
+        }
+        else if (bw > 0)
+          radius = (double)bw;
+        else
+        {  // B0 = N0: the shortest row below d_eff, here from the rows' doubles (an estimate's radius)
+          bh.resize(dd * nn);
+          GCHK(hipMemcpy2D(bh.data(), nn * 8, g->P.b + (size_t)(first_lattice + w) * dd * g->P.ldn, (size_t)g->P.ldn * 8,
+                           nn * 8, dd, hipMemcpyDeviceToHost));
+          radius = std::numeric_limits<double>::infinity();
+          for (int i = 0; i < d_eff; ++i)
+          {
+            double acc = 0.0;
+            for (size_t j = 0; j < nn; ++j)
+              acc += (double)bh[i * nn + j] * (double)bh[i * nn + j];
+            radius = std::min(radius, acc);
+          }
+        }
+        // the radius never falls below the K-th norm: B0 is the safe side of the estimate
+        if (fphip_enum_gh_nodes(d_eff, rd.data(), pruning, radius) > lim)
+          take[w] = 0;
+      }
+    }
+  }
+  const bool any_wave = std::find(take.begin(), take.end(), 1) != take.end();
+  const bool all_wave = std::find(take.begin(), take.end(), 0) == take.end();
+  if (any_wave)
+    if (int rc = svp_best_wave_run(g, first_lattice, count, K, bound_sq, pruning, all_wave ? nullptr : take.data(), found,
+                                   sol_coord, vec, norm, nodes, status))
+      return rc;
+  const float wave_ms = g->last_ms;
+  for (int w = 0; w < count; ++w)
+  {
+    if (take[w])
+      continue;
+    if (gst[first_lattice + w] != 1)
+    {
+      memset(sol_coord + (size_t)w * kk * dd, 0, kk * dd * sizeof(int64_t));
+      memset(vec + (size_t)w * kk * nn, 0, kk * nn * sizeof(int64_t));
+      memset(norm + (size_t)w * kk, 0, kk * sizeof(int64_t));
+      found[w] = 0, nodes[w] = 0, status[w] = 0;
+      continue;
+    }
+    if (int rc = svp_best_enum_one(g, ectx, first_lattice + w, K, bound_sq ? bound_sq[w] : 0, pruning, found + w,
+                                   sol_coord + (size_t)w * kk * dd, vec + (size_t)w * kk * nn, norm + (size_t)w * kk,
+                                   nodes + w, status + w))
+      return rc;
+  }
+  g->last_ms = wave_ms;
+  return FPHIP_OK;
+}
+
 // ---- lists of short / near vectors (list_vectors.hip; the enumeration: fphip_enum_list) ----------------------------
 // the vector kernel over m records of one lattice: vec [m][n], norm [m], status [m]
 static int list_vectors_run(fphip_gso *g, int lattice, uint64_t m, const int64_t *coef, const int64_t *target, int64_t *vec,

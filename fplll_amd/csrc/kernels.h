@@ -135,6 +135,25 @@ struct SvpWave
 };
 template <int NQ> __global__ void svp_wave_kernel(GsoBatch P, SvpWave A);
 
+// svp_best.hip: the max_sols shortest vectors of every lattice of the range, one wave per lattice
+struct SvpBestWave
+{
+  int first, count;
+  int stack_doubles, mu_doubles;  // per wave, in LDS: as SvpWave
+  int max_sols;                   // K, 1 .. 64: the table's norms and its rank-to-slot map sit across the lanes
+  const double *pruning;          // [d] or null (every coefficient 1)
+  const int *take;                // [count] or null: 0 = this lattice goes another route, its outputs are left alone
+  const long long *bound;         // [count] or null: the caller's bound on the squared norm; 0 = the default (N0)
+  long long *rec;                 // [count][K][d] work space: the kept coefficient records by slot
+  long long *sol_coord;           // [count][K][d] by rank; entries beyond found are zero
+  long long *vec;                 // [count][K][n]
+  long long *norm;                // [count][K]
+  int *found;                     // [count] <= K
+  unsigned long long *nodes;      // [count] fplll's counting rule
+  int *status;                    // [count] 1 RED_SUCCESS, 0 update_gso failed, -2 beyond 63 bits (outputs zero)
+};
+template <int NQ> __global__ void svp_best_kernel(GsoBatch P, SvpBestWave A);
+
 // cvp_wave.hip: the closest-vector solver, one wave per target of ONE lattice; the inputs are the device outputs of
 // the preparation (CvpPrep) and the true mu / r_ii of cvp_unscale_kernel
 struct CvpWave

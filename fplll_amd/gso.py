@@ -666,6 +666,57 @@ class MatGSOBatch:
         self._chk(rc, "shortest_vector")
         return sol, vec, norm, nodes, st
 
+    def shortest_vectors(self, max_sols, first=0, count=None, bound_sq=None, pruning=None, route="auto", ectx=None,
+                         method=0, flags=0):
+        """fphip_shortest_vectors: the ``max_sols`` (1 .. 64) shortest non-zero vectors, one of each pair +-v, of the
+        lattices [first, first + count) of the batch (LLL-reduced bases), decided on exact integer norms — the
+        reference's shortest_vectors(max_sols), a shrinking N-best.  ``bound_sq``: None (the default bound: the norm of
+        the shortest row), one integer for every lattice, or [count] integers (0 = the default for that lattice); only
+        vectors with norm <= the bound are kept.  ``route``: "wave" (one wavefront per lattice, d <= 64, the first
+        max_sols vectors in (norm, depth-first discovery) order, deterministic), "enum" (one enumerator call per
+        lattice; which of several vectors tied at the cut are kept is unspecified, the norms are not) or "auto".
+        Returns (found int32 [count], sol_coord int64 [count][max_sols][d], vec int64 [count][max_sols][n], norm int64
+        [count][max_sols] sorted, entries beyond found zero, nodes uint64 [count], status int32 [count]: 1, 0 =
+        update_gso failed, -2 = beyond 63 bits).  With ``pruning`` found may be 0 while status stays 1."""
+        K = int(max_sols)
+        if K != max_sols or K < 1 or K > 64:
+            raise ValueError("shortest_vectors: max_sols is an integer in 1 .. 64, got %r (longer lists: short_vectors)" % (max_sols,))
+        if route not in _lib.SVP_ROUTES:
+            raise ValueError("shortest_vectors: route is one of %s, got %r" % (", ".join(sorted(_lib.SVP_ROUTES)), route))
+        count = self.batch - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.batch:
+            raise ValueError("shortest_vectors: lattices [%d, %d) outside the batch of %d" % (first, first + count, self.batch))
+        bnd = None
+        if bound_sq is not None:
+            bnd = np.asarray(bound_sq)
+            if bnd.ndim == 0:
+                bnd = np.full(count, bnd)
+            if bnd.shape != (count,) or any(int(v) != v or v < 0 or v >= 2**63 for v in bnd.tolist()):
+                raise ValueError("shortest_vectors: bound_sq is None, a non-negative integer or [%d] of them, got %r" % (count, bound_sq))
+            bnd = np.ascontiguousarray([int(v) for v in bnd.tolist()], dtype=np.int64)
+        pr = None
+        if pruning is not None:
+            pr = np.ascontiguousarray(pruning, dtype=np.float64)
+            if pr.shape != (self.d,):
+                raise ValueError("shortest_vectors: pruning is [%d], got shape %r" % (self.d, pr.shape))
+        found = np.zeros(count, dtype=np.int32)
+        sol = np.zeros((count, K, self.d), dtype=np.int64)
+        vec = np.zeros((count, K, self.n), dtype=np.int64)
+        norm = np.zeros((count, K), dtype=np.int64)
+        nodes = np.zeros(count, dtype=np.uint64)
+        st = np.zeros(count, dtype=np.int32)
+        _lib.bind_shortest_vectors(self.lib)
+        rc = self.lib.fphip_shortest_vectors(
+            self.h, None if ectx is None else ectx.handle, first, count, K,
+            None if bnd is None else bnd.ctypes.data_as(ctypes.c_void_p), method, flags,
+            None if pr is None else pr.ctypes.data_as(ctypes.c_void_p), _lib.SVP_ROUTES[route],
+            *(a.ctypes.data_as(ctypes.c_void_p) for a in (found, sol, vec, norm, nodes, st)))
+        if rc == _lib.FPHIP_UNSUPPORTED:
+            from .enumeration import Unsupported
+            raise Unsupported("shortest_vectors declined by the device layer (d=%d): %s" % (self.d, self.ctx.last_error()))
+        self._chk(rc, "shortest_vectors")
+        return found, sol, vec, norm, nodes, st
+
     def records_to_vectors(self, coef, target=None, lattice=0):
         """fphip_list_records_to_vectors: for every row of ``coef`` (int64 [m][d]) the vector sum_i coef_i b_i (minus
         the int64 ``target`` [n] when given) and its exact squared norm.  Returns (vec int64 [m][n], norm int64 [m],

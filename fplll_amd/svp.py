@@ -9,6 +9,10 @@ exact integer norm; nothing here enumerates on the CPU.  Bases of at most 64 row
 ``shortest_vector`` / ``shortest_vector_batch`` are the reference's ``shortest_vector(b, sol_coord, SVPM_FAST)``
 (``fplll -a svp``) behind ``fphip_shortest_vector``: a wave-per-lattice kernel for batches of bases of at most 64 rows,
 the multi-wave enumerator for larger ones, the answer decided on exact integer norms on either route.
+
+``shortest_vectors`` / ``shortest_vectors_batch`` are the reference's ``shortest_vectors(..., max_sols)`` as such: the
+N <= 64 shortest vectors of every lattice of a batch under a radius that shrinks to the worst kept norm
+(``fphip_shortest_vectors``), no radius to guess and no list to cut afterwards.
 """
 import numpy as np
 
@@ -120,3 +124,61 @@ def shortest_vector(ctx, b, reduce=True, pruning=None, route="auto", ectx=None):
     b = _basis(b, "shortest_vector")
     sol, vec, norm = shortest_vector_batch(ctx, b[None], reduce=reduce, pruning=pruning, route=route, ectx=ectx)
     return sol[0], vec[0], int(norm[0])
+
+
+def shortest_vectors_batch(ctx, bs, max_sols, bound_sq=None, reduce=True, pruning=None, route="auto", ectx=None):
+    """The ``max_sols`` (1 .. 64) shortest non-zero vectors, one of each pair +-v, of every lattice of ``bs`` (int64
+    [B][d][n]): the reference's shortest_vectors(max_sols), one call for the batch.  ``bound_sq``: None (per lattice the
+    norm of its shortest row after the reduction: at least one vector is found), one non-negative integer, or [B] of
+    them (0 = the default); only vectors with norm <= the bound are kept, so fewer than ``max_sols`` may come back.
+    ``reduce=True`` runs the batched LLL first and expresses ``sol_coord`` in the caller's basis through u, in exact
+    Python integers.  ``pruning`` and ``route`` as in ``shortest_vector_batch``; on the "wave" route the answer is the
+    first max_sols vectors in (norm, depth-first discovery) order, on "enum" which of several vectors tied at the cut
+    are kept is unspecified.  Returns ``(found int32 [B], sol_coord [B][max_sols][d], vec int64 [B][max_sols][n], norm
+    int64 [B][max_sols])``, sorted by norm, entries beyond ``found`` zero.  With ``pruning`` a lattice may have found =
+    0 (the reference's RED_ENUM_FAILURE); raises ``HipError`` naming the lattice where a status is not RED_SUCCESS."""
+    b = np.ascontiguousarray(bs, dtype=np.int64)
+    if b.ndim != 3 or b.shape[0] < 1 or b.shape[1] < 1 or b.shape[1] > b.shape[2]:
+        raise ValueError("shortest_vectors_batch: bs is [B][d][n] with B >= 1 and 1 <= d <= n, got shape %r" % (b.shape,))
+    if int(max_sols) != max_sols or not 1 <= max_sols <= 64:
+        raise ValueError("shortest_vectors_batch: max_sols is an integer in 1 .. 64, got %r (longer lists: short_vectors)" % (max_sols,))
+    if route not in _lib.SVP_ROUTES:
+        raise ValueError("shortest_vectors_batch: route is one of %s, got %r" % (", ".join(sorted(_lib.SVP_ROUTES)), route))
+    if pruning is not None and np.shape(pruning) != (b.shape[1],):
+        raise ValueError("shortest_vectors_batch: pruning is [%d], got shape %r" % (b.shape[1], np.shape(pruning)))
+    if bound_sq is not None:
+        bq = np.asarray(bound_sq)
+        if bq.shape not in ((), (b.shape[0],)) or any(int(v) != v or v < 0 for v in bq.reshape(-1).tolist()):
+            raise ValueError("shortest_vectors_batch: bound_sq is None, a non-negative integer or [%d] of them, got %r" % (b.shape[0], bound_sq))
+    g = MatGSOBatch(ctx, b.shape[0], b.shape[1], b.shape[2])
+    try:
+        g.set_basis(b)
+        u = None
+        if reduce:
+            g.enable_transform()
+            status, _ = g.lll()
+            for k, s in enumerate(status):
+                if s != RED_SUCCESS:
+                    raise _lib.HipError("shortest_vectors: lll of lattice %d ended with status %d" % (k, s))
+            u = g.get_transform()
+        found, sol, vec, norm, _, status = g.shortest_vectors(int(max_sols), bound_sq=bound_sq, pruning=pruning, route=route, ectx=ectx)
+    finally:
+        g.close()
+    for k, s in enumerate(status):
+        if s != RED_SUCCESS:
+            raise _lib.HipError("shortest_vectors: lattice %d ended with status %d (%s)" % (
+                k, s, "an entry or a norm beyond 63 bits" if s == -2 else "update_gso failed"))
+    if u is not None:  # v = sol (u b_in): the coefficients in the caller's basis, exact
+        sol = np.stack([sol[k].astype(object).dot(u[k].astype(object)) for k in range(len(sol))])
+    return found, sol, vec, norm
+
+
+def shortest_vectors(ctx, b, max_sols, bound_sq=None, reduce=True, pruning=None, route="auto", ectx=None):
+    """``shortest_vectors_batch`` for one basis ``b`` (int64 [d][n]) and one ``bound_sq`` (None or an integer):
+    ``(found, sol_coord [max_sols][d], vec [max_sols][n], norm [max_sols])``."""
+    b = _basis(b, "shortest_vectors")
+    if bound_sq is not None and np.ndim(bound_sq) != 0:
+        raise ValueError("shortest_vectors: bound_sq is None or one non-negative integer, got %r" % (bound_sq,))
+    found, sol, vec, norm = shortest_vectors_batch(ctx, b[None], max_sols, bound_sq=bound_sq, reduce=reduce, pruning=pruning,
+                                                   route=route, ectx=ectx)
+    return int(found[0]), sol[0], vec[0], norm[0]

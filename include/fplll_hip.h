@@ -698,7 +698,7 @@ int fphip_list_records_to_vectors(fphip_gso *g, int lattice, uint64_t m, const i
  *          1 RED_SUCCESS, 0 update_gso failed, -2 a row norm or a candidate left the 63-bit range (outputs zero).
  * method: FPHIP_SVPM_FAST only — SVPM_PROVED (the exact evaluator) is declined; flags: 0 only — SVP_OVERRIDE_BND and
  * SVP_DUAL are declined.  Every decline is FPHIP_UNSUPPORTED with a fphip_last_error text before anything is launched.
- * Not offered: sub-solutions, auxiliary solutions, several ranks, entries beyond int64.
+ * Not offered: sub-solutions, several ranks, entries beyond int64 (auxiliary solutions: fphip_shortest_vectors below).
  * fphip_gso_last_kernel_ms: the WAVE launch (0 when every lattice went the ENUM route).
  */
 #define FPHIP_SVPM_FAST 0
@@ -711,6 +711,50 @@ int fphip_list_records_to_vectors(fphip_gso *g, int lattice, uint64_t m, const i
 int fphip_shortest_vector(fphip_gso *g, fphip_ctx *ectx, int first_lattice, int count, int method, int flags,
                           const double *pruning, int route, int64_t *sol_coord, int64_t *vec, int64_t *norm,
                           uint64_t *nodes, int *status);
+
+/*
+ * The N shortest vectors (ABI version 8).  fphip_shortest_vectors: the reference's
+ * shortest_vectors(gso, sol_coord, sol_dist, max_sols, ...) and the auxiliary-solution overload of
+ * shortest_vector_pruning (svpcvp.cpp:84-241, 446-454) — an enumeration under a BEST_N evaluator whose radius shrinks to
+ * the worst of the max_sols kept vectors — for the lattices [first_lattice, first_lattice + count) of g, on LLL-reduced
+ * bases of int64 entries, decided on EXACT integers.  Per lattice, after update_gso:
+ *   bound    B0 = bound_sq[w] where bound_sq is given and the entry is positive (0: the default), else N0, the exact
+ *            squared norm of the shortest row below last_useful_index (get_basis_min).  The walk starts at the radius
+ *            (double)B0 (1 + 2^-30): INCLUSIVE, unlike fphip_shortest_vector's N0 - 1 — a row of norm N0 is found by
+ *            the walk, nothing is seeded.
+ *   rows     without a caller's bound last_useful_index as fphip_shortest_vector has it (r_ii <= 2 r_00 on the true
+ *            r); with one the threshold is max(2 r_00, radius): a vector whose top non-zero coefficient sits on row j
+ *            has norm >= r_jj, so a row above the radius contributes nothing — the reference's 2 r_00 rule is sound
+ *            only for bounds <= 2 r_00 and would drop vectors under a larger one.  One row left: the multiples of b_0.
+ *   accept   a leaf with nd > 0 within the level bound is a candidate; its vector and norm nv are formed in integers
+ *            (a value beyond 63 bits: status -2, outputs zero).  It is accepted iff 0 < nv <= B0 and the table holds
+ *            fewer than max_sols entries or nv < the worst kept norm; it goes behind every kept entry with norm <= nv
+ *            and the worst entry leaves a full table.  Once the table is full the radius is (double)(worst - 1)
+ *            (1 + 2^-30) — norms are integers, only norm <= worst - 1 can still enter — and a full table with
+ *            worst = 1 ends the walk.  The 2^-30 is the margin of the other solvers: a heuristic allowance for the
+ *            rounding of the enumeration's doubles, not a proved error bound.  One of each pair +-v, never zero.
+ *   max_sols 1 .. 64, anything else is FPHIP_ERROR (longer lists: fphip_list_vectors, every vector within a radius);
+ *            a negative bound_sq entry is FPHIP_ERROR.  bound_sq is [count] or NULL.
+ *   route    FPHIP_SVP_ROUTE_WAVE: one wavefront per lattice, the whole range in one launch (svp_best.hip), d <= 64 —
+ *            more rows: FPHIP_UNSUPPORTED before any launch.  The walk is sequential in the reference's order: the
+ *            answer is the first max_sols vectors in (norm, depth-first discovery) order; two calls give identical arrays.
+ *            FPHIP_SVP_ROUTE_ENUM: one fphip_enum_run per lattice on `ectx` (NULL: the context of g), d <=
+ *            FPHIP_ENUM_MAX_DIM, the table on the host in 128-bit integers, never declined for being small.  The walk
+ *            is parallel: WHICH of several vectors tied at the cut are kept is unspecified, the norms are not; ties in
+ *            the output are in the coefficient order of fphip_list_vectors.
+ *            FPHIP_SVP_ROUTE_AUTO: for max_sols = 1 without a bound the decision of fphip_shortest_vector; otherwise
+ *            WAVE where d <= 64 and fphip_enum_gh_nodes at radius B0 is at most FPHIP_SVP_WAVE_MAX_NODES (the radius
+ *            never falls below the max_sols-th norm: B0 is the safe side), ENUM otherwise.
+ *   outputs  per lattice of the range: found [count] (<= max_sols), sol_coord [count][max_sols][d], vec
+ *            [count][max_sols][n], norm [count][max_sols] sorted by norm, entries beyond found zero; nodes [count]
+ *            (fplll's counting rule), status [count]: 1, 0 update_gso failed, -2 beyond 63 bits (outputs zero).
+ *            With pruning found may be 0 while status stays 1: the reference's RED_ENUM_FAILURE case.
+ * method: FPHIP_SVPM_FAST only; flags: 0 only — declined as fphip_shortest_vector declines them.
+ * Not offered: sub-solutions, max_sols > 64, several ranks, entries beyond int64.
+ */
+int fphip_shortest_vectors(fphip_gso *g, fphip_ctx *ectx, int first_lattice, int count, int max_sols,
+                           const int64_t *bound_sq, int method, int flags, const double *pruning, int route, int *found,
+                           int64_t *sol_coord, int64_t *vec, int64_t *norm, uint64_t *nodes, int *status);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Batched Householder R-factor: MatHouseholder<Z_NR<long>, FP_NR<double>> (householder.h:38)    */
