@@ -11,4 +11,5 @@ from .enumeration import (  # noqa: F401
 from .cvp import closest_vector, closest_vectors  # noqa: F401
 from .svp import (short_vectors, shortest_vector, shortest_vector_batch, shortest_vectors,  # noqa: F401
                   shortest_vectors_batch, theta_series, vectors_near)
-from .gram import MatGSOGramBatch, lll_reduction_gram  # noqa: F401
+from .gram import (MatGSOGramBatch, lll_reduction_gram, shortest_vector_gram, shortest_vectors_gram,  # noqa: F401
+                   sqnorm_coordinates)

@@ -129,6 +129,15 @@ def bind_shortest_vectors(lib):
     return lib.fphip_shortest_vectors
 
 
+def bind_gram_shortest_vectors(lib):
+    """Prototype of fphip_gram_shortest_vectors (h, ectx, first_form, count, max_sols, bound_sq, method, flags, pruning,
+    route, found, sol_coord, norm, nodes, status)."""
+    vp = ctypes.c_void_p
+    lib.fphip_gram_shortest_vectors.restype = ctypes.c_int
+    lib.fphip_gram_shortest_vectors.argtypes = [vp, vp] + [ctypes.c_int] * 3 + [vp] + [ctypes.c_int] * 2 + [vp, ctypes.c_int] + [vp] * 5
+    return lib.fphip_gram_shortest_vectors
+
+
 # fphip_closest_vector_ex: the routes, and the status of a walk its node budget ended (WAVE route only)
 CVP_ROUTES = {"auto": 0, "wave": 1, "enum": 2}
 CVP_NODE_LIMIT = 2

@@ -12,8 +12,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 
-HIP_SOURCES = ["enum_kernel.hip", "enum_walk.hip", "enum_kernel_cvp.hip", "enum_walk_cvp.hip", "enum_walk4.hip", "enum_walk5.hip", "enum_kernel_list.hip", "enum_walk_list.hip", "enum_kernel_cvp_list.hip", "enum_walk_cvp_list.hip", "enum_deal.hip", "enum_order.hip", "enum_host.hip", "gso_kernel.hip", "gso_sweep2.hip", "lll_kernel.hip", "lll_kernel_early.hip", "hlll_kernel.hip", "hh_blocked.hip", "hh_rows.hip", "hlll_x.hip", "lll_x.hip", "bkz_kernel.hip", "bkzs_kernel.hip", "bkz_kernel_u.hip", "bkzs_kernel_u.hip", "hlll_kernel_u.hip", "hlll_x_u.hip", "lll_x_u.hip", "gso_host.hip", "lll_gram.hip", "gram_host.hip", "cvp_prepare.hip", "list_vectors.hip", "svp_wave.hip", "svp_best.hip", "cvp_wave.hip", "pruner_volume.hip", "pruner_search.hip", "gso_util_host.hip"]
-HIP_HEADERS = ["dev_mem.h", "dev_cache.h", "trace.h", "pruner_tables.h", "pruner_engine.h", "enum_device.h", "enum_order.h", "enum_wave.h", "gso_device.h", "gram_device.h", "gso_wave.h", "gso_sweep2.h", "ftx.h", "lll_wave.h", "lll_stream.h", "kernels.h", "enum_kernels.h", "host_common.h", os.path.join(ROOT, "include", "fplll_hip.h")]
+HIP_SOURCES = ["enum_kernel.hip", "enum_walk.hip", "enum_kernel_cvp.hip", "enum_walk_cvp.hip", "enum_walk4.hip", "enum_walk5.hip", "enum_kernel_list.hip", "enum_walk_list.hip", "enum_kernel_cvp_list.hip", "enum_walk_cvp_list.hip", "enum_deal.hip", "enum_order.hip", "enum_host.hip", "gso_kernel.hip", "gso_sweep2.hip", "lll_kernel.hip", "lll_kernel_early.hip", "hlll_kernel.hip", "hh_blocked.hip", "hh_rows.hip", "hlll_x.hip", "lll_x.hip", "bkz_kernel.hip", "bkzs_kernel.hip", "bkz_kernel_u.hip", "bkzs_kernel_u.hip", "hlll_kernel_u.hip", "hlll_x_u.hip", "lll_x_u.hip", "gso_host.hip", "lll_gram.hip", "gram_host.hip", "cvp_prepare.hip", "list_vectors.hip", "svp_wave.hip", "svp_best.hip", "svp_gram.hip", "cvp_wave.hip", "pruner_volume.hip", "pruner_search.hip", "gso_util_host.hip"]
+HIP_HEADERS = ["dev_mem.h", "dev_cache.h", "trace.h", "pruner_tables.h", "pruner_engine.h", "enum_device.h", "enum_order.h", "enum_wave.h", "gso_device.h", "gram_device.h", "gso_wave.h", "gso_sweep2.h", "ftx.h", "lll_wave.h", "lll_stream.h", "kernels.h", "enum_kernels.h", "host_common.h", "svp_host.h", os.path.join(ROOT, "include", "fplll_hip.h")]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17",
     "-ffp-contract=off",  # fplll's arithmetic is separate mul/add (nr/nr_FP_d.inl:178); no FMA
@@ -60,6 +60,8 @@ PER_FILE_FLAGS = {
     "svp_wave.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
     # the N-shortest-vectors solver: svp_wave.hip's loops under a table of kept norms, the same flag
     "svp_best.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
+    # the N shortest vectors of a quadratic form: svp_best.hip's loops with the Gram evaluator, the same flag
+    "svp_gram.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
     # the closest-vector solver's wave-per-target walk: svp_wave.hip's loops with a target, the same flag
     "cvp_wave.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],
     "hlll_kernel.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"],

@@ -170,7 +170,7 @@ static int fail(fphip_ctx *ctx, const char *fmt, ...)
       return fail(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" int fphip_abi_version(void) { return 8; }
+extern "C" int fphip_abi_version(void) { return 9; }
 
 extern "C" int fphip_device_count(void)
 {

@@ -1,13 +1,16 @@
 // gram_host.hip — C ABI (include/fplll_hip.h, fphip_gram_*) for batches of integer quadratic forms on the device:
-// MatGSOGram<Z_NR<long>, FP_NR<double>>(g, u, u_inv_t, GSO_INT_GRAM) with update_gso() and
-// LLLReduction<Z_NR<long>, FP_NR<double>>::lll().  The kernels are in lll_gram.hip.
+// MatGSOGram<Z_NR<long>, FP_NR<double>>(g, u, u_inv_t, GSO_INT_GRAM) with update_gso(),
+// LLLReduction<Z_NR<long>, FP_NR<double>>::lll() and shortest_vectors(MatGSOGram, ...).  The kernels are in
+// lll_gram.hip and svp_gram.hip.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -15,6 +18,7 @@
 #include "dev_mem.h"
 #include "host_common.h"
 #include "kernels.h"
+#include "svp_host.h"
 #include "trace.h"
 
 using namespace fphip;
@@ -325,3 +329,372 @@ extern "C" int fphip_gram_lll(fphip_gram *h, double delta, double eta, int flags
 }
 
 extern "C" double fphip_gram_last_kernel_ms(const fphip_gram *h) { return h ? (double)h->last_ms : 0.0; }
+
+// ---- the N shortest vectors of a form (svp_gram.hip; the ENUM route: fphip_enum_run under the host table) -----------
+namespace
+{
+typedef __int128 i128;
+// the ENUM route's exact candidate: x G x^T by the steps of svp_gram.hip
+struct GramCand
+{
+  int d;               // rows under enumeration (d_eff)
+  int ld;              // the host copy's row stride (the form's d)
+  const long long *g;  // [d][ld] host copy of the form
+  bool overflow;
+};
+// false: the norm is beyond 63 bits (or a coefficient is 2^57 and more); *norm = 0 for a negative value (an
+// indefinite form the doubles did not catch): the table does not accept it
+bool svp_exact_candidate(GramCand *C, const double *sol, long long *norm)
+{
+  const int d = C->d;
+  for (int i = 0; i < d; ++i)
+    if (!(std::fabs(sol[i]) < 144115188075855872.0))  // 2^57: below it no step leaves the 128 bits
+      return false;
+  i128 H = 0, L = 0;
+  for (int j = 0; j < d; ++j)
+  {
+    const long long xj = (long long)sol[j];
+    if (xj == 0)
+      continue;
+    i128 y = 0;
+    for (int i = 0; i < d; ++i)
+      y += (i128)(long long)sol[i] * (i128)C->g[(size_t)i * C->ld + j];
+    const long long yh          = (long long)(y >> 64);
+    const unsigned long long yl = (unsigned long long)y;
+    H += (i128)xj * (i128)yh;
+    L += (i128)xj * (i128)(unsigned __int128)yl;
+  }
+  const i128 T = H + (L >> 64);  // x G x^T = T 2^64 + (the low word of L)
+  const long long lo = (long long)(unsigned long long)L;
+  if (T < 0)
+  {
+    *norm = 0;
+    return true;
+  }
+  if (T != 0 || lo < 0)
+    return false;
+  *norm = lo;
+  return true;
+}
+}  // namespace
+
+// the wave-per-form kernel over the range; outputs of the forms with take_h[w] == 0 are left alone
+static int svp_gram_wave_run(fphip_gram *h, int first, int count, int K, const int64_t *bound_sq, const double *pruning,
+                             const int *take_h, int *found, int64_t *sol_coord, int64_t *norm, uint64_t *nodes,
+                             int *status)
+{
+  const size_t d = h->P.d, kk = (size_t)K;
+  int wpb        = 4;
+  SvpGramWave A;
+  memset(&A, 0, sizeof A);
+  A.first = first, A.count = count, A.max_sols = K;
+  A.stack_doubles = (int)(d * (d + 1) / 2 + 2);
+  A.mu_doubles    = (int)std::max<size_t>(d * (d - 1) / 2, 2);
+  const size_t per_wave = (size_t)(A.stack_doubles + A.mu_doubles) * sizeof(double);
+  const size_t lds      = per_wave * wpb;  // d <= 64: at most 131136 bytes
+  int bpc = (int)((160 * 1024) / lds);
+  if (bpc * wpb > 32)
+    bpc = 32 / wpb;
+  int grid = (count + wpb - 1) / wpb;
+  int cap  = fphip_ctx_num_cus(h->ctx) * std::max(bpc, 1);
+  if (const char *e = getenv("FPHIP_SVP_WAVE_GRID"))  // (tests: a small grid makes a small batch go round the grid-stride loop)
+    cap = std::max(1, atoi(e));
+  grid = std::min(grid, cap);
+  hipStream_t s = fphip_ctx_stream(h->ctx);
+  CvpBufs B(s);
+  double *pr_d = nullptr;
+  int *take_d  = nullptr;
+  long long *bound_d = nullptr;
+  QCHK(B.get(&A.rec, (size_t)count * kk * d));
+  QCHK(B.get(&A.sol_coord, (size_t)count * kk * d));
+  QCHK(B.get(&A.norm, (size_t)count * kk));
+  QCHK(B.get(&A.found, (size_t)count));
+  QCHK(B.get(&A.nodes, (size_t)count));
+  QCHK(B.get(&A.status, (size_t)count));
+  if (pruning)
+  {
+    QCHK(B.get(&pr_d, d));
+    QCHK(hipMemcpy(pr_d, pruning, d * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (take_h)
+  {
+    QCHK(B.get(&take_d, (size_t)count));
+    QCHK(hipMemcpy(take_d, take_h, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (bound_sq)
+  {
+    QCHK(B.get(&bound_d, (size_t)count));
+    QCHK(hipMemcpy(bound_d, bound_sq, (size_t)count * sizeof(long long), hipMemcpyHostToDevice));
+  }
+  QCHK(hipStreamSynchronize(nullptr));  // (see fphip_gram_set)
+  A.pruning = pr_d;
+  A.take    = take_d;
+  A.bound   = bound_d;
+  if (lds > 64 * 1024)
+    QCHK(allow_lds(svp_gram_kernel, lds));
+  QCHK(hipEventRecord(h->ev[0], s));
+  hipLaunchKernelGGL(svp_gram_kernel, dim3(grid), dim3(wpb * 64), lds, s, h->P, A);
+  QCHK(hipGetLastError());
+  QCHK(hipEventRecord(h->ev[1], s));
+  QCHK(hipStreamSynchronize(s));
+  QCHK(hipEventElapsedTime(&h->last_ms, h->ev[0], h->ev[1]));
+  if (!take_h)
+  {  // the whole range: straight into the caller's arrays
+    QCHK(hipMemcpy(sol_coord, A.sol_coord, (size_t)count * kk * d * sizeof(long long), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(norm, A.norm, (size_t)count * kk * sizeof(long long), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(found, A.found, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(nodes, A.nodes, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(status, A.status, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return FPHIP_OK;
+  }
+  for (int w = 0; w < count; ++w)
+  {
+    if (!take_h[w])
+      continue;
+    QCHK(hipMemcpy(sol_coord + (size_t)w * kk * d, A.sol_coord + (size_t)w * kk * d, kk * d * sizeof(long long), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(norm + (size_t)w * kk, A.norm + (size_t)w * kk, kk * sizeof(long long), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(found + w, A.found + w, sizeof(int), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(nodes + w, A.nodes + w, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy(status + w, A.status + w, sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return FPHIP_OK;
+}
+
+// one form by the enumerator under the host table: gh [d][d], mu [d][d], rd [d] host copies; outputs [K][d], [K]
+static int svp_gram_enum_one(fphip_gram *h, fphip_ctx *ectx, int form, int K, long long bound, const double *pruning,
+                             const long long *gh, const double *mu, const double *rd, int *found, int64_t *sol,
+                             int64_t *norm, uint64_t *nodes, int *status)
+{
+  const int d = h->P.d;
+  const size_t dd = (size_t)d, kk = (size_t)K;
+  memset(sol, 0, kk * dd * sizeof(int64_t));
+  memset(norm, 0, kk * sizeof(int64_t));
+  *found = 0, *nodes = 0, *status = 1;
+  for (size_t i = 0; i < dd; ++i)
+    if (gh[i * dd + i] <= 0)
+    {
+      *status = 0;
+      return FPHIP_OK;
+    }
+  long long B0 = bound;
+  int d_eff;
+  if (bound > 0)
+    d_eff = svp_best_rows(d, rd, true, (double)bound * (1.0 + 0x1p-30));
+  else
+  {
+    d_eff = svp_best_rows(d, rd, false, 0.0);
+    B0    = gh[0];
+    for (int i = 1; i < d_eff; ++i)
+      B0 = std::min(B0, gh[(size_t)i * dd + i]);
+  }
+  for (int i = 0; i < d_eff; ++i)
+    if (!(rd[i] > 0.0 && std::isfinite(rd[i])))
+    {
+      *status = 0;  // not positive definite on the rows walked, as far as the doubles see
+      return FPHIP_OK;
+    }
+  SvpTable<GramCand> T{GramCand{d_eff, d, gh, false}, K, B0, {}, {}};
+  if (T.radius0() > 0.0)
+  {
+    if (d_eff == 1)
+      *nodes = svp_table_line(&T, rd[0], pruning ? pruning[0] : 1.0);  // the multiples of the first variable
+    else
+    {
+      const size_t de = (size_t)d_eff;
+      std::vector<double> mut(de * de, 0.0);
+      for (size_t i = 0; i < de; ++i)
+        for (size_t j = i + 1; j < de; ++j)
+          mut[i * de + j] = mu[j * dd + i];  // the layout a plugin receives: mut[i][j] = mu(j,i), j > i
+      fphip_enum_opts o;
+      memset(&o, 0, sizeof o);
+      o.shard_count       = 1;
+      o.exchange_chunks   = 1;
+      o.min_nodes_decline = 0;  // never declined for being small
+      std::vector<uint64_t> nd(FPHIP_ENUM_MAX_DIM + 1, 0);
+      const int rc = fphip_enum_run(ectx, d_eff, T.radius0(), mut.data(), rd, pruning, &o, svp_table_cb<GramCand>, nullptr,
+                                    &T, nd.data(), nullptr);
+      if (rc != FPHIP_OK)
+      {
+        if (ectx != h->ctx)
+          snprintf(fphip_ctx_errbuf(h->ctx), 512, "fphip_gram_shortest_vectors: enumeration of form %d: %s", form,
+                   fphip_last_error(ectx));
+        return rc;
+      }
+      for (int k = 0; k <= d_eff; ++k)
+        *nodes += nd[k];
+    }
+  }
+  if (T.cand.overflow)
+  {
+    *status = -2;
+    *nodes  = 0;
+    return FPHIP_OK;
+  }
+  // ties in the coefficient order of fphip_list_vectors (from level d - 1 down): the arrival order is the parallel walk's
+  const std::vector<size_t> ord = T.order();
+  for (size_t o = 0; o < ord.size(); ++o)
+  {
+    const std::vector<long long> &xi = T.x[ord[o]];
+    for (int i = 0; i < d_eff; ++i)
+      sol[o * dd + i] = xi[i];
+    norm[o] = T.norms[ord[o]];
+  }
+  *found = (int)ord.size();
+  return FPHIP_OK;
+}
+
+extern "C" int fphip_gram_shortest_vectors(fphip_gram *h, fphip_ctx *ectx, int first_form, int count, int max_sols,
+                                           const int64_t *bound_sq, int method, int flags, const double *pruning,
+                                           int route, int *found, int64_t *sol_coord, int64_t *norm, uint64_t *nodes,
+                                           int *status)
+{
+  FPHIP_RANGE("fphip_gram_shortest_vectors");
+  if (!h)
+    return FPHIP_ERROR;
+  if (!found || !sol_coord || !norm || !nodes || !status)
+    return fail_msg(h->ctx, "fphip_gram_shortest_vectors: found, sol_coord, norm, nodes and status are all required");
+  if (!ectx)
+    ectx = h->ctx;
+  if (first_form < 0 || count <= 0 || first_form > h->P.batch - count)
+    return fail_msg(h->ctx, "fphip_gram_shortest_vectors: forms [first_form, first_form + count) outside the batch");
+  char *err = fphip_ctx_errbuf(h->ctx);
+  if (max_sols < 1 || max_sols > 64)
+  {
+    snprintf(err, 512, "fphip_gram_shortest_vectors: max_sols = %d is outside 1 .. 64", max_sols);
+    return FPHIP_ERROR;
+  }
+  bool any_bound = false;
+  if (bound_sq)
+    for (int w = 0; w < count; ++w)
+    {
+      if (bound_sq[w] < 0)
+        return fail_msg(h->ctx, "fphip_gram_shortest_vectors: a negative bound_sq (0 = the default bound)");
+      any_bound = any_bound || bound_sq[w] > 0;
+    }
+  if (method != FPHIP_SVPM_FAST)
+  {
+    snprintf(err, 512, "fphip_gram_shortest_vectors: method %d (SVPM_PROVED and its exact evaluator, or an unknown one) is "
+             "not offered: SVPM_FAST only", method);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (flags != 0)
+  {
+    snprintf(err, 512, "fphip_gram_shortest_vectors: flags 0x%x (SVP_DUAL, SVP_OVERRIDE_BND, or unknown ones) are not "
+             "offered: 0 only", flags);
+    return FPHIP_UNSUPPORTED;
+  }
+  const int d = h->P.d, K = max_sols;
+  if (route != FPHIP_SVP_ROUTE_AUTO && route != FPHIP_SVP_ROUTE_WAVE && route != FPHIP_SVP_ROUTE_ENUM)
+    return fail_msg(h->ctx, "fphip_gram_shortest_vectors: unknown route");
+  if (route == FPHIP_SVP_ROUTE_WAVE && d > 64)
+  {
+    snprintf(err, 512, "fphip_gram_shortest_vectors: the WAVE route takes at most 64 rows (d = %d): use the ENUM route", d);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (d > FPHIP_ENUM_MAX_DIM)
+  {  // (not reachable today: fphip_gram_create declines d > 256 = FPHIP_ENUM_MAX_DIM; kept so that the two limits stay
+     //  independent — fphip_shortest_vectors has the same line)
+    snprintf(err, 512, "fphip_gram_shortest_vectors: more than %d rows", FPHIP_ENUM_MAX_DIM);
+    return FPHIP_UNSUPPORTED;
+  }
+  if (pruning)
+    for (int i = 0; i < d; ++i)
+      if (!(pruning[i] > 0.0) || !std::isfinite(pruning[i]))
+        return fail_msg(h->ctx, "fphip_gram_shortest_vectors: a pruning coefficient that is not a positive finite number");
+  std::vector<int> gst(h->P.batch, 0);
+  if (int rc = fphip_gram_update(h, gst.data()))
+    return rc;
+  h->last_ms = 0.0f;
+  const size_t dd = (size_t)d, ldd = (size_t)h->P.ldd, kk = (size_t)K;
+  // the route of every form of the range: 1 = WAVE
+  std::vector<int> take((size_t)count, route == FPHIP_SVP_ROUTE_ENUM || d > 64 ? 0 : 1);
+  const bool auto_est = route == FPHIP_SVP_ROUTE_AUTO && d <= 64;
+  // host copies for the estimate and the enumerator: r_ii of the range; the form and mu of one form at a time
+  std::vector<double> rs;
+  if (auto_est || route != FPHIP_SVP_ROUTE_WAVE)
+  {
+    rs.resize((size_t)count * dd);
+    QCHK(hipMemcpy(rs.data(), h->P.rdg + (size_t)first_form * dd, rs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  std::vector<long long> gh(dd * dd), diag;
+  std::vector<double> muh(dd * dd);
+  if (auto_est)
+  {
+    const char *e    = getenv("FPHIP_SVP_WAVE_MAX_NODES");
+    const double lim = e ? atof(e) : SVP_WAVE_MAX_NODES_DEFAULT;
+    if (lim > 0.0)
+    {
+      const bool as_one = K == 1 && !any_bound;  // the decision of fphip_shortest_vector
+      for (int w = 0; w < count; ++w)
+      {
+        if (gst[first_form + w] != 1)
+          continue;  // (the kernel reports it)
+        const double *rd   = &rs[(size_t)w * dd];
+        const long long bw = bound_sq ? bound_sq[w] : 0;
+        const int d_eff    = svp_best_rows(d, rd, bw > 0, (double)bw * (1.0 + 0x1p-30));
+        bool pos = true;
+        for (int i = 0; i < d_eff; ++i)
+          pos = pos && rd[i] > 0.0 && std::isfinite(rd[i]);
+        if (!pos)
+          continue;
+        double radius;
+        if (as_one)
+        {
+          double logdet = 0.0;
+          for (int i = 0; i < d_eff; ++i)
+            logdet += std::log(rd[i]);
+          const double gh2 = std::exp((2.0 / d_eff) * (std::lgamma(0.5 * d_eff + 1.0) - 0.5 * d_eff * std::log(M_PI) + 0.5 * logdet));
+          radius = std::min(rd[0], gh2);
+        }
+        else if (bw > 0)
+          radius = (double)bw;
+        else
+        {  // B0: the smallest diagonal entry below d_eff, as a double (an estimate's radius)
+          if (diag.empty())
+          {  // the diagonals of the whole range, once: one copy of the forms, not one per form
+            diag.resize((size_t)count * dd);
+            std::vector<long long> all((size_t)count * dd * ldd);
+            QCHK(hipMemcpy(all.data(), h->P.g + (size_t)first_form * dd * ldd, all.size() * 8, hipMemcpyDeviceToHost));
+            for (size_t f = 0; f < (size_t)count; ++f)
+              for (size_t i = 0; i < dd; ++i)
+                diag[f * dd + i] = all[f * dd * ldd + i * (ldd + 1)];
+          }
+          radius = std::numeric_limits<double>::infinity();
+          for (int i = 0; i < d_eff; ++i)
+            radius = std::min(radius, (double)diag[(size_t)w * dd + i]);
+        }
+        // the radius never falls below the K-th norm: B0 is the safe side of the estimate
+        if (fphip_enum_gh_nodes(d_eff, rd, pruning, radius) > lim)
+          take[w] = 0;
+      }
+    }
+  }
+  const bool any_wave = std::find(take.begin(), take.end(), 1) != take.end();
+  const bool all_wave = std::find(take.begin(), take.end(), 0) == take.end();
+  if (any_wave)
+    if (int rc = svp_gram_wave_run(h, first_form, count, K, bound_sq, pruning, all_wave ? nullptr : take.data(), found,
+                                   sol_coord, norm, nodes, status))
+      return rc;
+  const float wave_ms = h->last_ms;
+  for (int w = 0; w < count; ++w)
+  {
+    if (take[w])
+      continue;
+    if (gst[first_form + w] != 1)
+    {
+      memset(sol_coord + (size_t)w * kk * dd, 0, kk * dd * sizeof(int64_t));
+      memset(norm + (size_t)w * kk, 0, kk * sizeof(int64_t));
+      found[w] = 0, nodes[w] = 0, status[w] = 0;
+      continue;
+    }
+    const size_t L = (size_t)(first_form + w);
+    QCHK(hipMemcpy2D(gh.data(), dd * 8, h->P.g + L * dd * ldd, ldd * 8, dd * 8, dd, hipMemcpyDeviceToHost));
+    QCHK(hipMemcpy2D(muh.data(), dd * 8, h->P.mu + L * dd * ldd, ldd * 8, dd * 8, dd, hipMemcpyDeviceToHost));
+    if (int rc = svp_gram_enum_one(h, ectx, first_form + w, K, bound_sq ? bound_sq[w] : 0, pruning, gh.data(), muh.data(),
+                                   &rs[(size_t)w * dd], found + w, sol_coord + (size_t)w * kk * dd, norm + (size_t)w * kk,
+                                   nodes + w, status + w))
+      return rc;
+  }
+  h->last_ms = wave_ms;
+  return FPHIP_OK;
+}

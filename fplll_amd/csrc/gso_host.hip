@@ -38,6 +38,7 @@ __attribute__((visibility("hidden"))) int prune_block(VolumeEngine *eng, int n, 
 
 #include "host_common.h"
 #include "kernels.h"
+#include "svp_host.h"
 using namespace fphip;
 
 struct fphip_gso
@@ -2829,27 +2830,8 @@ extern "C" int fphip_gso_get_row_expo(fphip_gso *g, int lattice, int64_t *row_ex
 // ---- closest vectors: target preparation, MatGSOInterface::babai, the solver (cvp_prepare.hip) -------------------
 namespace
 {
-// device blocks of one call, back to the cache when it returns
-struct CvpBufs
-{
-  hipStream_t s;
-  std::vector<void *> ptrs;
-  explicit CvpBufs(hipStream_t s_) : s(s_) {}
-  ~CvpBufs()
-  {
-    for (void *p : ptrs)
-      fphip_dev_free(p, s);
-  }
-  template <class T> hipError_t get(T **p, size_t count)
-  {
-    void *q            = nullptr;
-    const hipError_t e = fphip_dev_alloc(&q, (count ? count : 1) * sizeof(T), s);
-    if (e == hipSuccess)
-      ptrs.push_back(q);
-    *p = (T *)q;
-    return e;
-  }
-};
+// (CvpBufs — the device blocks of one call, back to the cache when it returns — is in svp_host.h: gram_host.hip
+//  uses it too)
 }  // namespace
 
 static int cvp_lattice_guard(fphip_gso *g, int lattice, int T, const char *what)
@@ -3417,12 +3399,7 @@ extern "C" int fphip_closest_vector(fphip_gso *g, fphip_ctx *ectx, int lattice, 
 // ---- shortest vectors (svp_wave.hip; the ENUM route: fphip_enum_run) -----------------------------------------------
 namespace
 {
-// The default of FPHIP_SVP_WAVE_MAX_NODES: the Gaussian-heuristic node estimate (radius min(r_00, GH^2)) up to which
-// the AUTO route gives a lattice to the wave-per-lattice kernel.  Measured (profiles/svp_solver.md, LLL-reduced q-ary
-// lattices, batch 1024): at d = 32 (estimate 5.8e4) WAVE takes 0.179 ms per lattice against ENUM's 0.625 ms, at d = 40
-// (estimate 5.0e6) 31.9 ms against 1.43 ms; the two times are equal at an estimate of 2.08e5 (log-log interpolation).
-// 0 would mean no limit.
-constexpr double SVP_WAVE_MAX_NODES_DEFAULT = 2.0e5;
+// (SVP_WAVE_MAX_NODES_DEFAULT, the default of FPHIP_SVP_WAVE_MAX_NODES, is in svp_host.h: the forms' solver uses it too)
 
 typedef __int128 i128;
 // the ENUM route's evaluator: the candidate's exact norm in 128-bit integers, strictly smaller wins, the bound
@@ -3489,16 +3466,6 @@ double svp_best_cb(void *user, double dist, const double *sol)
       B->v[j] = (long long)B->w[j];
   }
   return B->bound();  // (0 once the norm is 1: nothing non-zero is shorter)
-}
-
-// last_useful_index (svpcvp.cpp:32-43) on the true r_ii
-int svp_last_useful_index(int d, const double *rd)
-{
-  int i;
-  for (i = d - 1; i > 0; --i)
-    if (rd[i] <= 2.0 * rd[0])
-      break;
-  return i + 1;
 }
 }  // namespace
 
@@ -3769,67 +3736,8 @@ extern "C" int fphip_shortest_vector(fphip_gso *g, fphip_ctx *ectx, int first_la
 }
 
 // ---- the N shortest vectors (svp_best.hip; the ENUM route: fphip_enum_run under a host table) ------------------------
-namespace
-{
-// the ENUM route's BEST_N evaluator: at most K records sorted by exact norm, ties in arrival order; the accept rule
-// and the radius are those of svp_best.hip
-struct SvpTable
-{
-  SvpBest cand;  // the exact candidate (d = the rows under enumeration)
-  int K;
-  long long B0;
-  std::vector<long long> norms;           // sorted
-  std::vector<std::vector<long long>> x;  // [found][d_eff]
-  double radius0() const { return (double)B0 * (1.0 + 0x1p-30); }
-  // the radius after a candidate: unchanged until the table is full, then (worst - 1) (1 + 2^-30); 0 = stop
-  double bound() const
-  {
-    if ((int)norms.size() < K)
-      return radius0();
-    return (double)(norms.back() - 1) * (1.0 + 0x1p-30);
-  }
-  void offer(long long nv, const double *sol)
-  {
-    const bool full = (int)norms.size() == K;
-    if (!(nv > 0 && nv <= B0 && (!full || nv < norms.back())))
-      return;
-    const size_t p = (size_t)(std::upper_bound(norms.begin(), norms.end(), nv) - norms.begin());
-    norms.insert(norms.begin() + p, nv);
-    std::vector<long long> xi((size_t)cand.d);
-    for (int i = 0; i < cand.d; ++i)
-      xi[i] = (long long)sol[i];
-    x.insert(x.begin() + p, xi);
-    if ((int)norms.size() > K)
-      norms.pop_back(), x.pop_back();
-  }
-};
-double svp_table_cb(void *user, double dist, const double *sol)
-{
-  (void)dist;  // (the decision is the integers')
-  SvpTable *T  = (SvpTable *)user;
-  long long nv = 0;
-  if (!svp_exact_candidate(&T->cand, sol, &nv))
-  {
-    T->cand.overflow = true;
-    return 0.0;  // stop
-  }
-  T->offer(nv, sol);
-  return T->bound();  // (0 once the table is full with worst = 1: nothing non-zero is shorter)
-}
-
-// the rows under enumeration: last_useful_index without a caller's bound; with one the threshold max(2 r_00, radius)
-int svp_best_rows(int d, const double *rd, bool has_bound, double radius0)
-{
-  if (!has_bound)
-    return svp_last_useful_index(d, rd);
-  const double thr = std::max(2.0 * rd[0], radius0);
-  int i;
-  for (i = d - 1; i > 0; --i)
-    if (rd[i] <= thr)
-      break;
-  return i + 1;
-}
-}  // namespace
+// (the table, the rows under enumeration and the walk of a single row are in svp_host.h: the quadratic forms'
+//  entry point of gram_host.hip uses them as well)
 
 // the wave-per-lattice kernel over the range; outputs of the lattices with take_h[w] == 0 are left alone
 static int svp_best_wave_run(fphip_gso *g, int first, int count, int K, const int64_t *bound_sq, const double *pruning,
@@ -3963,24 +3871,11 @@ static int svp_best_enum_one(fphip_gso *g, fphip_ctx *ectx, int lattice, int K, 
     d_eff = svp_best_rows(d, rd.data(), false, 0.0);
     B0    = *std::min_element(rn.begin(), rn.begin() + d_eff);
   }
-  SvpTable T{SvpBest{d_eff, n, bh.data(), 0, false, {}, {}, std::vector<i128>(nn)}, K, B0, {}, {}};
+  SvpTable<SvpBest> T{SvpBest{d_eff, n, bh.data(), 0, false, {}, {}, std::vector<i128>(nn)}, K, B0, {}, {}};
   if (T.radius0() > 0.0)
   {
     if (d_eff == 1)
-    {  // the multiples of b_0, as the walk steps through them: x = 1, 2, ... while the leaf is within the level bound
-      const double p0 = pruning ? pruning[0] : 1.0;
-      double radius   = T.radius0();
-      *nodes          = 1;  // (the leaf x = 0)
-      for (double x = 1.0;; x += 1.0)
-      {
-        if (!(x * x * rd[0] <= p0 * radius))
-          break;
-        ++*nodes;
-        radius = svp_table_cb(&T, 0.0, &x);
-        if (radius == 0.0)
-          break;
-      }
-    }
+      *nodes = svp_table_line(&T, rd[0], pruning ? pruning[0] : 1.0);  // the multiples of b_0
     else
     {
       const size_t de = (size_t)d_eff;
@@ -3994,7 +3889,7 @@ static int svp_best_enum_one(fphip_gso *g, fphip_ctx *ectx, int lattice, int K, 
       o.exchange_chunks   = 1;
       o.min_nodes_decline = 0;  // never declined for being small
       std::vector<uint64_t> nd(FPHIP_ENUM_MAX_DIM + 1, 0);
-      const int rc = fphip_enum_run(ectx, d_eff, T.radius0(), mut.data(), rd.data(), pruning, &o, svp_table_cb, nullptr, &T,
+      const int rc = fphip_enum_run(ectx, d_eff, T.radius0(), mut.data(), rd.data(), pruning, &o, svp_table_cb<SvpBest>, nullptr, &T,
                                     nd.data(), nullptr);
       if (rc != FPHIP_OK)
       {
@@ -4014,17 +3909,7 @@ static int svp_best_enum_one(fphip_gso *g, fphip_ctx *ectx, int lattice, int K, 
     return FPHIP_OK;
   }
   // ties in the coefficient order of fphip_list_vectors (from level d - 1 down): the arrival order is the parallel walk's
-  std::vector<size_t> ord(T.norms.size());
-  for (size_t i = 0; i < ord.size(); ++i)
-    ord[i] = i;
-  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
-    if (T.norms[a] != T.norms[b])
-      return T.norms[a] < T.norms[b];
-    for (size_t k = (size_t)d_eff; k-- > 0;)
-      if (T.x[a][k] != T.x[b][k])
-        return T.x[a][k] < T.x[b][k];
-    return a < b;
-  });
+  const std::vector<size_t> ord = T.order();
   std::vector<double> xd((size_t)d_eff);
   for (size_t o = 0; o < ord.size(); ++o)
   {

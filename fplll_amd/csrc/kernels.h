@@ -180,6 +180,24 @@ template <int NQ> __global__ void cvp_wave_kernel(GsoBatch P, CvpWave A);
 template <int NQ> __global__ void lll_gram_kernel(GramBatch P, double delta, double eta, double logdelta, int siegel);
 template <int NQ> __global__ void gram_update_kernel(GramBatch P);
 
+// svp_gram.hip: the max_sols shortest vectors of every quadratic form of the range, one wave per form (d <= 64)
+struct SvpGramWave
+{
+  int first, count;
+  int stack_doubles, mu_doubles;  // per wave, in LDS: as SvpWave
+  int max_sols;                   // K, 1 .. 64: the table's norms and its rank-to-slot map sit across the lanes
+  const double *pruning;          // [d] or null (every coefficient 1)
+  const int *take;                // [count] or null: 0 = this form goes another route, its outputs are left alone
+  const long long *bound;         // [count] or null: the caller's bound on x G x^T; 0 = the default (min g_ii)
+  long long *rec;                 // [count][K][d] work space: the kept coefficient records by slot
+  long long *sol_coord;           // [count][K][d] by rank; entries beyond found are zero
+  long long *norm;                // [count][K]
+  int *found;                     // [count] <= K
+  unsigned long long *nodes;      // [count] fplll's counting rule
+  int *status;                    // [count] 1, 0 update failed / not positive definite, -2 beyond 63 bits (outputs zero)
+};
+__global__ void svp_gram_kernel(GramBatch P, SvpGramWave A);
+
 }  // namespace fphip
 
 #endif

@@ -875,6 +875,38 @@ int fphip_gram_get_transform(fphip_gram *h, int64_t *u);
 int fphip_gram_lll(fphip_gram *h, double delta, double eta, int flags, int *status, int *info);
 double fphip_gram_last_kernel_ms(const fphip_gram *h);
 
+/*
+ * The N shortest vectors of quadratic forms (ABI version 9).  fphip_gram_shortest_vectors: the
+ * reference's shortest_vectors(MatGSOGram, sol_coord, sol_dist, max_sols, method, flags) (svpcvp.h:47-53,
+ * svpcvp.cpp:276-454, which reads mu, r and get_int_gram(i, i) only) for the forms [first_form, first_form + count) of
+ * h — LLL-reduced forms of int64 entries, no basis anywhere — decided on EXACT integers.  It runs fphip_gram_update
+ * first.  The semantics, the argument checks and the routes are those of fphip_shortest_vectors above, with
+ *   row norms  the diagonal g_ii; the default bound B0 is the smallest g_ii below last_useful_index; a form with a
+ *              diagonal entry <= 0: status 0;
+ *   rows       r_ii <= 2 r_00 on r directly, with a caller's bound max(2 r_00, radius); an r_ii among the rows walked
+ *              that is <= 0 or not finite: status 0, outputs zero (indefinite, semidefinite, rank-deficient forms), as
+ *              for a form whose update status is not 1;
+ *   candidate  N = x G x^T exactly: y = x G in 128-bit integers, N = sum_j x_j y_j split at 2^64 (DESIGN 3i has the
+ *              argument why no step leaves the 128 bits for coefficients below 2^57).  Status -2 (outputs zero, nodes
+ *              zero) is a candidate whose N is beyond 63 bits (or a coefficient of 2^57 and more);
+ *   outputs    found [count], sol_coord [count][max_sols][d] by rank (coefficients in the variables of the form as it
+ *              stands in h), norm [count][max_sols], nodes [count], status [count]; no vec: there is no ambient space.
+ * bound_sq [count] or NULL is indexed by the place in the range, 0 = the default.  FPHIP_UNSUPPORTED (nothing launched,
+ * no output written): a method other than FPHIP_SVPM_FAST, a non-zero flag, the WAVE route with d > 64, d >
+ * FPHIP_ENUM_MAX_DIM.  FPHIP_ERROR (likewise): max_sols outside 1 .. 64, a negative bound, a NULL output, a range
+ * outside the batch, a pruning coefficient that is not positive and finite.
+ *   route  WAVE: svp_gram.hip, one wavefront per form, the range in one launch, the first max_sols vectors in (norm,
+ *          depth-first discovery) order; ENUM: one fphip_enum_run per form on `ectx` (NULL: the context of h) under
+ *          the host table of fphip_shortest_vectors, d <= FPHIP_ENUM_MAX_DIM, never declined for being small; AUTO:
+ *          the decision procedure of fphip_shortest_vectors with g_ii in place of the row norms, the same
+ *          FPHIP_SVP_WAVE_MAX_NODES and the same default — measured on bases, NOT retuned for forms.
+ * fphip_gram_last_kernel_ms reports the wave launch (0 when every form went to the enumerator).
+ * Not offered: list mode, closest vectors relative to a form, SVP_DUAL, SVPM_PROVED, entries beyond int64.
+ */
+int fphip_gram_shortest_vectors(fphip_gram *h, fphip_ctx *ectx, int first_form, int count, int max_sols,
+                                const int64_t *bound_sq, int method, int flags, const double *pruning, int route,
+                                int *found, int64_t *sol_coord, int64_t *norm, uint64_t *nodes, int *status);
+
 #ifdef __cplusplus
 }
 #endif
